@@ -13,16 +13,20 @@ events ("scaling": "strong", BASELINE's config).  --scaling weak gives every ran
 1M keys instead.  There is no data-path collective: RCCL only all-gathers the per-rank
 counts/checksums and reduces the watermark (min of the ranks' max event time).
 
-    python bench.py                      # N=1, defaults finish in a few minutes
+    python bench.py                      # N=1: the headline figure alone, a few seconds
+    python bench.py --full               # N=1: every figure below, a few minutes
+    python bench.py --dump-outputs DIR   # + the last timed step's matches as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 
 Prints ONE JSON line on rank 0 (fields documented in DESIGN.md §7).  `roofline` prices
 cep_nfa_jit at SURVEY §8(d)'s algorithmic bytes (columns read once + 4 B per emitted event id +
-4 B per match) against 8 TB/s; `cpu_baseline` times the oracle (oracle/cep_oracle.cpp, the
-literal restatement of the reference NFA) on a 1/8 key sample on this host's cores.  At N=1
-the line also carries config 2 (`secondary`), the arrival-order end-to-end figure, the JSON
-ingest figure and configs 4/5 (`other_configs`), each with key errors, emitted event ids,
-roofline and a CPU baseline.
+4 B per match) against 8 TB/s, from the HIP events of the timed steps themselves.  A plain run
+sets up, warms up, times the steps and prints that line.  With --full the line also carries
+the match checksum and the lane balance, and at N=1 `cpu_baseline` (the oracle,
+oracle/cep_oracle.cpp, the literal restatement of the reference NFA, on a 1/8 key sample on
+this host's cores), config 2 (`secondary`), the projected scaling, the streaming and processor
+figures, the arrival-order end-to-end figure, the JSON ingest figure and configs 4/5
+(`other_configs`), each with key errors, emitted event ids, roofline and a CPU baseline.
 """
 import argparse
 import json
@@ -642,6 +646,56 @@ def ingest(device, steps, keys, cpu_sample):
     return res
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+
+
+def _exact_float(v):
+    """v (integers) as float32 where that holds every value exactly, else as float64"""
+    return v.astype(np.float32 if v.size == 0 or max(int(v.max()), -int(v.min())) < 1 << 24 else np.float64)
+
+
+def _seeded_sample(item_bytes, budget):
+    """Sorted indices of a fixed sample of the items whose sizes sum to at most `budget`: the
+    longest prefix of a seeded permutation that fits (every item when they all fit)."""
+    if int(item_bytes.sum()) <= budget:
+        return np.arange(len(item_bytes))
+    perm = np.random.default_rng(0).permutation(len(item_bytes))
+    keep = int(np.searchsorted(np.cumsum(item_bytes[perm]), budget, side="right"))
+    return np.sort(perm[:keep])
+
+
+def dump_outputs(sess, n_keys, out_dir, rank=0):
+    """What a caller of the timed path receives after its last step, as out_dir/<name>.npy:
+    Session.matches (per match its key, emitting event and the offset of its first event in
+    pair_seq/pair_stage, which list the matched events and their stages, all in the reference's
+    order) and Session.key_errors (per key the exception code and its event).  Every value is
+    an integer below 2^53: float32 where an array stays below 2^24, else float64.  At most
+    DUMP_BYTES in all: a quarter for the key errors, the rest for the matches.  Where an output
+    is larger, a fixed seeded sample of whole keys and of whole matches is written (the same
+    ones in every run), pair_off rebased to the sampled matches' events."""
+    m = sess.matches(0)
+    code, seq = sess.key_errors(0, n_keys)
+    # (a key's error position means something only where the key has an error)
+    code, seq = _exact_float(code), _exact_float(np.where(code != 0, seq, 0))
+    ks = _seeded_sample(np.full(n_keys, code.itemsize + seq.itemsize, np.int64), DUMP_BYTES // 4)
+    arrays = {"key_error_code": code[ks], "key_error_seq": seq[ks]}
+    key, emit, off = _exact_float(m["key"]), _exact_float(m["emit_seq"]), m["pair_off"].astype(np.int64)
+    pseq, pstage = _exact_float(m["pair_seq"]), _exact_float(m["pair_stage"])
+    n_pairs = np.diff(off)
+    # 8 bytes for a match's pair_off entry (float64 at worst, and one entry more than matches)
+    ms = _seeded_sample(key.itemsize + emit.itemsize + 8 + n_pairs * (pseq.itemsize + pstage.itemsize),
+                        DUMP_BYTES - DUMP_BYTES // 4 - 8)
+    new_off = np.zeros(len(ms) + 1, np.int64)
+    np.cumsum(n_pairs[ms], out=new_off[1:])
+    # positions of the sampled matches' events in pair_seq / pair_stage
+    ev = np.repeat(off[:-1][ms] - new_off[:-1], n_pairs[ms]) + np.arange(new_off[-1])
+    arrays.update(key=key[ms], emit_seq=emit[ms], pair_off=_exact_float(new_off), pair_seq=pseq[ev],
+                  pair_stage=pstage[ev])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + (f"_rank{rank}" if rank else "") + ".npy"), v)
+
+
 def _partition_ms(s):
     off, perm, ms = N.C.c_void_p(), N.C.c_void_p(), N.C.c_double()
     N._check(N.lib().cep_batch_layout(s.h, N.CEP_MEM_DEVICE, N.C.byref(off), N.C.byref(perm), N.C.byref(ms)))
@@ -657,6 +711,11 @@ def main():
     ap.add_argument("--mean", type=int, default=1000, help="mean events per key")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"])
     ap.add_argument("--variant", default="readme", choices=["readme", "test"])
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checksum, lane balance, CPU baselines and every other configuration and "
+                         "figure (the --no-* options below drop parts of it)")
     ap.add_argument("--cpu-threads", type=int, default=cpu_share()[0])
     ap.add_argument("--cpu-every", type=int, default=8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -694,16 +753,19 @@ def main():
     log(f"cfg3: {stream.n_keys} keys, {stream.n_events} events on rank {dist.rank}")
     el, kms, aux_ms = run_steps(sess, stream, args.steps, args.warmup, dist, ts)
     log(f"cfg3: {1e3 * el / args.steps:.2f} ms per step")
+    if args.dump_outputs:
+        dump_outputs(sess, stream.n_keys, args.dump_outputs, dist.rank)
     n_m, n_pairs, n_err = match_figures(sess, 0, stream.n_keys)
     st = sess.stats(0)
-    try:
-        bal_ordered, bal_identity = sess.lane_balance(0)
-    except N.CepError:  # (no estimate ran: a shard of <= 64 keys)
-        bal_ordered = bal_identity = None
-    digest = global_digest(sess, key_ids)
     wm = dist.min_i64(sess.watermark())
     per = dist.gather([stream.n_events, n_m, n_pairs, el, kms, float(n_err), stream.n_keys])
-    checksum = dist.sum_u64(digest)  # wrapping sum of the shards' checksums (global key ids)
+    if args.full:
+        try:
+            bal_ordered, bal_identity = sess.lane_balance(0)
+        except N.CepError:  # (no estimate ran: a shard of <= 64 keys)
+            bal_ordered = bal_identity = None
+        # wrapping sum of the shards' checksums (global key ids)
+        checksum = dist.sum_u64(global_digest(sess, key_ids))
     tot_ev, tot_m, tot_p = per[:, 0].sum(), per[:, 1].sum(), per[:, 2].sum()
     t_max = per[:, 3].max()
 
@@ -736,13 +798,14 @@ def main():
             "roofline": roofline(alg, st["main_ms"], "cep_nfa_jit", step_kernels_ms=kms, compaction_ms=aux_ms,
                                  est_order_bits_ms=st["kernel_ms"] - st["main_ms"] - st["retry_ms"],
                                  retry_ms=st["retry_ms"]),
+            "watermark": wm,
+        }
+        if args.full:
             # north_star's wave divergence figure: sum over 64-lane waves of the busiest lane's
             # work estimate / the mean lane's, in the launch's lane order and in key order
-            "lane_balance": {"wave_max_over_mean": bal_ordered, "without_lane_order": bal_identity},
-            "watermark": wm,
-            "checksum": f"{checksum:016x}",
-        }
-        one = dist.world == 1
+            out["lane_balance"] = {"wave_max_over_mean": bal_ordered, "without_lane_order": bal_identity}
+            out["checksum"] = f"{checksum:016x}"
+        one = dist.world == 1 and args.full  # every figure below takes runs of its own
         cpu = one and not args.no_cpu_baseline
         if cpu:
             log("cfg3 cpu baseline")

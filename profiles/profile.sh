@@ -5,7 +5,7 @@
 # usage: bash profiles/profile.sh <tag> [bench args...]
 set -o pipefail
 TAG=${1:-r01}; shift
-ARGS=${@:---keys 200000 --steps 2 --warmup 1 --no-cpu-baseline}
+ARGS=${@:---full --keys 200000 --steps 2 --warmup 1 --no-cpu-baseline}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
