@@ -349,6 +349,31 @@ int cep_symbol_keys(int device, const uint8_t* bytes, const uint64_t* rec_off, c
                     const int32_t* status, uint64_t n_records, uint64_t max_symbols, uint32_t* key_out,
                     uint64_t* n_symbols, void* stream);
 
+/* ---- schema-driven ingest: JSON record values -> typed event columns (on the device) ----
+ * The same json-simple grammar and CEP_JSON_* outcomes as cep_decode_stock_json, followed by typed
+ * getters over a field table: fields[f] names a top-level key and the type of its column
+ * (the IR's codes: 1 int, 2 long, 3 double); cols[f] is a device column of n_records values of
+ * 4, 8, 8 bytes.  int and long take an INT token ((Long) o.get(name); an int outside int32 is
+ * CEP_JSON_NARROW), double an INT or DOUBLE token (((Number) o.get(name)).doubleValue(), the
+ * token's value Double.valueOf(text): correctly rounded).  A key matches when its unescaped text
+ * equals the name; for duplicate keys the last value wins.  span_field (optional) names one
+ * string-valued key whose text span[2r..2r+1] gets in name_span's encoding, so cep_symbol_keys
+ * keys the batch unchanged.  Outcome per record, first failure: top value null (NULL) or not an
+ * object (CLASS_CAST); the span field neither String nor null (CLASS_CAST); the fields in table
+ * order (absent or null: NULL; wrong kind: CLASS_CAST); then this decoder's own limits, NARROW
+ * and CEP_JSON_PRECISION: a decimal whose rounding the device conversion cannot prove (never a
+ * wrong bit).  Failed records get 0 in every column.  1..32 fields; names are 1..64 bytes of
+ * ASCII, distinct (span_field included), else CEP_E_INVALID before any launch.  Asynchronous on
+ * `stream`; n_records == 0 is a no-op. */
+#define CEP_JSON_PRECISION 8
+typedef struct {
+  const char* name;
+  uint8_t type;
+} cep_json_field;
+int cep_decode_json(int device, const uint8_t* bytes, const uint64_t* rec_off, uint64_t n_records,
+                    const cep_json_field* fields, uint32_t n_fields, void* const* cols,
+                    const char* span_field, uint32_t* span, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,12 @@ uint64_t stencil_tiles(uint64_t n_events);
 hipError_t launch_decode_stock_json(const uint8_t* bytes, const uint64_t* rec_off, uint64_t n, int col_width,
                                     void* price, void* volume, int32_t* status, uint32_t* name_span,
                                     hipStream_t st);
+namespace jsong {
+struct Table;
+}
+// ingest_generic.hip: the schema-driven decoder (pow5: json_generic.h build_pow5_table, on the device)
+hipError_t launch_decode_json(const uint8_t* bytes, const uint64_t* rec_off, uint64_t n, const jsong::Table& tab,
+                              const uint64_t* pow5, uint32_t* span, int32_t* status, hipStream_t st);
 hipError_t launch_max(const int64_t* ts, uint64_t n, unsigned long long* out, hipStream_t st);
 struct Node;
 hipError_t launch_live_floor(const Node* nodes, uint64_t n_nodes, uint64_t n_keys, uint32_t* floor, hipStream_t st);

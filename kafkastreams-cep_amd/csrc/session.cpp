@@ -1,6 +1,6 @@
 // session.cpp — the C ABI (include/cep.h): query compile, sessions on one GPU, batch
 // matching, result retrieval.  Host code; kernels live in nfa.hip / stencil.hip / partition.hip /
-// ingest.hip / symbol.hip / shard.hip / watermark.hip (the synthetic generators of the bench
+// ingest.hip / ingest_generic.hip / symbol.hip / shard.hip / watermark.hip (the synthetic generators of the bench
 // and the tests are a separate library, synth_gen.hip -> libcep_synth.so).
 #include <hip/hip_runtime.h>
 
@@ -12,11 +12,13 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "cep_internal.h"
+#include "json_generic.h"
 #include "kernel_args.h"
 #include "stencil_args.h"
 
@@ -1755,6 +1757,43 @@ int cep_decode_stock_json(int device, const uint8_t* bytes, const uint64_t* rec_
     HIPCHECK(hipSetDevice(device));
     HIPCHECK(launch_decode_stock_json(bytes, rec_off, n_records, col_width, price, volume, status, name_span,
                                       (hipStream_t)stream));
+  });
+}
+
+// the powers-of-five table of cep_decode_json's number path: built on the host at first use,
+// uploaded once per device on the caller's stream and waited for (never freed: it lives as long
+// as the library)
+static const uint64_t* json_pow5(int device, hipStream_t st) {
+  static std::mutex mu;
+  static std::vector<uint64_t> host;
+  static std::vector<std::pair<int, uint64_t*>> dev;
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& d : dev)
+    if (d.first == device) return d.second;
+  if (host.empty()) {
+    host.resize(2 * jsong::kPow5Count);
+    jsong::build_pow5_table(host.data());
+  }
+  uint64_t* p = nullptr;
+  HIPCHECK(hipMalloc((void**)&p, host.size() * 8));
+  copy_sync(p, host.data(), host.size() * 8, hipMemcpyHostToDevice, st);
+  dev.emplace_back(device, p);
+  return p;
+}
+
+int cep_decode_json(int device, const uint8_t* bytes, const uint64_t* rec_off, uint64_t n_records,
+                    const cep_json_field* fields, uint32_t n_fields, void* const* cols,
+                    const char* span_field, uint32_t* span, int32_t* status, void* stream) {
+  if (!rec_off || !status || (!bytes && n_records) || (span_field && !span))
+    return fail(CEP_E_INVALID, "null argument");
+  jsong::Table tab;
+  if (const char* msg = jsong::fill_table(&tab, fields, n_fields, cols, span_field)) return fail(CEP_E_INVALID, msg);
+  return guarded([&] {
+    DeviceGuard g(device);
+    HIPCHECK(hipSetDevice(device));
+    if (n_records == 0) return;
+    HIPCHECK(launch_decode_json(bytes, rec_off, n_records, tab, json_pow5(device, (hipStream_t)stream),
+                                span_field ? span : nullptr, status, (hipStream_t)stream));
   });
 }
 

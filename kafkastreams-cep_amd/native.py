@@ -31,6 +31,7 @@ EXPORTS = [
     "cep_batch_layout", "cep_session_snapshot", "cep_session_restore",
     "cep_decode_stock_json", "cep_jit_precompile_group", "cep_query_group_plan",
     "cep_last_stats", "cep_gather_keys", "cep_timing_totals", "cep_symbol_keys", "cep_lane_balance",
+    "cep_decode_json",
 ]
 # every symbol include/cep_synth.h declares (the generator library of the bench and tests)
 SYNTH_EXPORTS = ["cep_synth_last_error", "cep_synth_count", "cep_synth_generate", "cep_synth_generate_arrival",
@@ -67,6 +68,10 @@ class Matches(C.Structure):
                 ("emit_seq", C.POINTER(C.c_uint32)), ("pair_off", C.POINTER(C.c_uint64)),
                 ("pair_seq", C.POINTER(C.c_uint32)), ("pair_stage", C.POINTER(C.c_uint16)),
                 ("memory", C.c_int)]
+
+
+class JsonField(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_uint8)]
 
 
 _lib = None
@@ -116,6 +121,8 @@ def lib():
             "cep_live_floor": ([vp, C.c_int, C.POINTER(u32), u64], C.c_int),
             "cep_decode_stock_json": ([C.c_int, vp, vp, u64, C.c_int, vp, vp, vp, vp, vp], C.c_int),
             "cep_symbol_keys": ([C.c_int, vp, vp, vp, vp, u64, u64, vp, C.POINTER(u64), vp], C.c_int),
+            "cep_decode_json": ([C.c_int, vp, vp, u64, C.POINTER(JsonField), u32, C.POINTER(vp), C.c_char_p, vp, vp,
+                                 vp], C.c_int),
             "cep_lane_balance": ([vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         }
         for name, (args, res) in sig.items():
@@ -441,6 +448,50 @@ def decode_stock_json(batch: StockJsonBatch, col_width: int = 8, out: DecodedSto
     _check(lib().cep_decode_stock_json(batch.device, batch.data.ptr, batch.rec_off.ptr, batch.n, col_width,
                                        out.price.ptr, out.volume.ptr, out.status.ptr,
                                        out.name_span.ptr if out.name_span is not None else None, stream))
+    out._src = batch  # the launch is asynchronous: keep the input's device buffers alive with the output
+    return out
+
+
+JsonBatch = StockJsonBatch  # record values back to back + u64 offsets: nothing in it is StockEvent's
+
+
+class DecodedJson:
+    """Device columns of a JsonBatch decoded against an EventSchema: one DeviceBuffer per schema
+    column (int 4 bytes; long, double 8), the status, and the span of `span_field`'s text
+    (`name_span`, what symbol_keys reads).  `cols` are DeviceStream / ArrivalStream columns as
+    they are."""
+    _DT = {1: np.int32, 2: np.int64, 3: np.float64}
+
+    def __init__(self, n, schema, span_field=None, device=0):
+        if any(t not in self._DT for t in schema.types):
+            raise CepError("decode_json decodes int, long and double columns")
+        self.n, self.names, self.types, self.span_field = int(n), list(schema.names), list(schema.types), span_field
+        self.cols = [DeviceBuffer((4 if t == 1 else 8) * max(1, n), device) for t in self.types]
+        self.status = DeviceBuffer(4 * max(1, n), device)
+        self.name_span = DeviceBuffer(8 * max(1, n), device) if span_field is not None else None
+
+    def download(self):
+        out = {nm: c.download(self._DT[t], self.n) for nm, t, c in zip(self.names, self.types, self.cols)}
+        out["status"] = self.status.download(np.int32, self.n)
+        if self.name_span is not None:
+            out["name_span"] = self.name_span.download(np.uint32, 2 * self.n).reshape(-1, 2)
+        return out
+
+
+def decode_json(batch: JsonBatch, schema, span_field: str | None = None, out: DecodedJson | None = None,
+                stream=None) -> DecodedJson:
+    """cep_decode_json: the batch's records -> one typed column per schema field (top-level keys
+    by name), one launch, asynchronous on `stream`."""
+    if out is None:
+        out = DecodedJson(batch.n, schema, span_field, batch.device)
+    assert out.n == batch.n and out.names == list(schema.names) and out.types == list(schema.types)
+    assert out.span_field == span_field
+    enc = lambda s: s if isinstance(s, bytes) else s.encode()  # noqa: E731
+    fields = (JsonField * max(1, len(out.names)))(*[JsonField(enc(nm), t) for nm, t in zip(out.names, out.types)])
+    ptrs = (C.c_void_p * max(1, len(out.cols)))(*[c.ptr for c in out.cols])
+    _check(lib().cep_decode_json(batch.device, batch.data.ptr, batch.rec_off.ptr, batch.n, fields, len(out.names),
+                                 ptrs, None if span_field is None else enc(span_field),
+                                 out.name_span.ptr if out.name_span is not None else None, out.status.ptr, stream))
     out._src = batch  # the launch is asynchronous: keep the input's device buffers alive with the output
     return out
 
