@@ -97,7 +97,9 @@ typedef struct {
 
 #define CEP_KIND_NFA 0      /* general NFA kernel (runs, shared versioned buffer, folds) */
 #define CEP_KIND_STENCIL 1  /* proven specialisation: all stages ONE + strict, total
-                               state-free predicates, distinct names */
+                               state-free predicates, distinct names; range
+                               predicates over int, long and double columns take its fast
+                               path (cep_query_stencil_plan) */
 
 /* Compile a serialised Pattern chain.  On a reference compile-time exception the call
  * still succeeds and info.compile_error says which (sessions then refuse the query). */
@@ -122,6 +124,21 @@ int cep_jit_precompile_group(const cep_query* const* queries, int n_queries, dou
 int cep_query_group_plan(const cep_query* const* queries, int n_queries, int group, const char** source,
                          uint32_t* n_members, const int32_t** members, uint32_t* n_literals,
                          const int64_t** literals);
+/* How the mask pass of a CEP_KIND_STENCIL query reads its events: the range fast path (every
+ * stage a conjunction of `field OP constant`, OP in < <= > >= ==, over at most two columns of
+ * int, long or double - the columns streamed with 16-B loads and compared as intervals, a mixed
+ * pair listed int first) or interpreted predicates (anything else: a field under a cast, !=,
+ * OR, NOT, arithmetic, ts, a third column).  (Introspection.) */
+typedef struct {
+  uint32_t range;        /* 1: stencil_mask runs the range fast path; 0: interpreted predicates */
+  uint32_t n_cols;       /* columns the fast path streams (1 or 2; 0 when range == 0) */
+  uint32_t col_field[2]; /* their field indices */
+  uint8_t  col_type[2];  /* the type each column is read as, IR type codes: 1 int, 2 long, 3 double.
+                            It is the field's own type, except when no stage constrains any column
+                            (every predicate `true`): then field 0 is streamed as int whatever its
+                            type, and every value is accepted */
+} cep_stencil_plan;
+int cep_query_stencil_plan(const cep_query* q, cep_stencil_plan* out);  /* CEP_E_INVALID for a CEP_KIND_NFA query */
 
 #define CEP_TIER_JIT 0     /* NFA queries run their own kernel, generated and compiled by hipRTC */
 #define CEP_TIER_INTERP 1  /* NFA queries run the precompiled bytecode-interpreter kernel */

@@ -26,10 +26,11 @@ struct cep_query {
   // CEP_KIND_STENCIL
   std::vector<uint16_t> arityStage;   // walk order stage names
   std::vector<uint16_t> stencilProg;  // predicate program per pattern (first..last)
-  bool stencilRange = false;          // every predicate is a conjunction of int ranges
+  bool stencilRange = false;          // every predicate is a conjunction of ranges (compile.cpp Ranges)
   int rangeCols[2] = {0, 0};
+  uint8_t rangeType[2] = {1, 1};      // IR types of rangeCols (a mixed pair: the int first)
   int nRangeCols = 0;
-  int64_t rangeLo[8][2]{}, rangeHi[8][2]{};
+  int64_t rangeLo[8][2]{}, rangeHi[8][2]{};  // per stage and column, stencil_args.h RangeStage
   // semantic WITHIN (IR v2 flag): epsilon stages keep their source stage's
   // window, so runs expire (the reference's own WITHIN never prunes: parity mode)
   bool semantic = false;

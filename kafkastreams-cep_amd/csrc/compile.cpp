@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <functional>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -174,13 +175,26 @@ bool total(const Expr* e) {  // evaluation can never throw
   return total(e->a.get()) && total(e->b.get());
 }
 
+// The order key of a double (stencil_args.h RangeStage): int64 keys compare as the doubles do
+// in IEEE / Java, -0.0 and +0.0 are the adjacent keys -1 and 0, NaNs lie beyond the infinities.
+int64_t okey(double d) {
+  int64_t b;
+  std::memcpy(&b, &d, 8);
+  return b ^ ((b >> 63) & INT64_MAX);
+}
+
 // Interval form of a predicate for the stencil fast path: a conjunction of comparisons of
-// int fields with constants -> lo <= field <= hi per field.
+// int, long or double fields with constants -> lo <= field <= hi per field, closed, in the
+// field's own order (a double's bounds as order keys).  INT64_MIN..INT64_MAX: unconstrained.
 struct Ranges {
-  int field[2] = {-1, -1};
+  int field[2] = {-1, -1}, type[2] = {0, 0};
   int64_t lo[2] = {INT64_MIN, INT64_MIN}, hi[2] = {INT64_MAX, INT64_MAX};
   int n = 0;
-  bool add(int f, int64_t l, int64_t h) {
+  bool add(int f, int t, int64_t l, int64_t h) {
+    if (t == 3) {  // a constrained double fails a NaN event on either side
+      l = std::max(l, okey(-INFINITY));
+      h = std::min(h, okey(INFINITY));
+    }
     for (int i = 0; i < n; i++)
       if (field[i] == f) {
         lo[i] = std::max(lo[i], l);
@@ -189,6 +203,7 @@ struct Ranges {
       }
     if (n == 2) return false;
     field[n] = f;
+    type[n] = t;
     lo[n] = l;
     hi[n] = h;
     n++;
@@ -196,33 +211,70 @@ struct Ranges {
   }
 };
 
-const Expr* int_field(const Expr* e, const std::vector<int>& ftypes) {
-  if (e->op == 0x18 && e->t2 == 1 && e->t == 2) e = e->a.get();  // (long) int_field
-  if (e->op == 0x05 && ftypes[e->idx] == 1) return e;
-  return nullptr;
+// the field of a comparison of type `ct`: bare and of that type, or (long) int_field
+const Expr* range_field(const Expr* e, const std::vector<int>& ftypes, int ct) {
+  if (e->op == 0x18 && e->t2 == 1 && e->t == 2) {
+    e = e->a.get();
+    return e->op == 0x05 && ftypes[e->idx] == 1 ? e : nullptr;
+  }
+  if (e->op != 0x05) return nullptr;
+  const int ft = ftypes[e->idx];
+  return ft == ct || (ft == 1 && ct == 2) ? e : nullptr;
+}
+
+// the constant of a comparison: a literal, or one under explicit widening casts folded as Java
+// does ((double) long rounds to nearest even, as the host's conversion)
+bool range_const(const Expr* c, int* t, int64_t* i, double* d) {
+  switch (c->op) {
+    case 0x01: case 0x02: *t = c->t; *i = c->i; return true;
+    case 0x03: *t = 3; *d = c->d; return true;
+    case 0x18:
+      if (!range_const(c->a.get(), t, i, d) || *t != c->t2 || c->t <= c->t2 || c->t > 3) return false;
+      if (c->t == 3) *d = (double)*i;
+      *t = c->t;
+      return true;
+  }
+  return false;
 }
 
 bool ranges_of(const Expr* e, const std::vector<int>& ftypes, Ranges& r) {
   if (e->op == 0x04) return e->i != 0;  // `true` adds nothing (false: not a range)
   if (e->op == 0x30) return ranges_of(e->a.get(), ftypes, r) && ranges_of(e->b.get(), ftypes, r);
-  if (e->op < 0x20 || e->op > 0x24 || (e->t2 != 1 && e->t2 != 2)) return false;
-  const Expr* f = int_field(e->a.get(), ftypes);
+  if (e->op < 0x20 || e->op > 0x24 || e->t2 < 1 || e->t2 > 3) return false;
+  const Expr* f = range_field(e->a.get(), ftypes, e->t2);
   const Expr* c = e->b.get();
   int op = e->op;
   if (!f) {  // const OP field  ->  field OP' const
-    f = int_field(e->b.get(), ftypes);
+    f = range_field(e->b.get(), ftypes, e->t2);
     c = e->a.get();
     static const int flip[5] = {0x22, 0x23, 0x20, 0x21, 0x24};  // lt->gt, le->ge, gt->lt, ge->le
     op = flip[op - 0x20];
   }
-  if (!f || !(c->op == 0x01 || c->op == 0x02)) return false;
-  const int64_t k = c->i;
+  int ct = 0;
+  int64_t k = 0;
+  double d = 0;
+  if (!f || !range_const(c, &ct, &k, &d) || (ct == 3) != (e->t2 == 3)) return false;
+  const int ft = ftypes[f->idx];
+  if (ct == 3) {
+    // x < k ends at the largest double below k and x > k starts at the smallest above it (the
+    // neighbouring keys); a zero bound takes the zero that keeps both or neither; a NaN bound
+    // is never true
+    if (std::isnan(d)) return r.add(f->idx, ft, 1, 0);
+    const bool z = d == 0;
+    switch (op) {
+      case 0x20: return r.add(f->idx, ft, INT64_MIN, okey(z ? -0.0 : d) - 1);
+      case 0x21: return r.add(f->idx, ft, INT64_MIN, okey(z ? 0.0 : d));
+      case 0x22: return r.add(f->idx, ft, okey(z ? 0.0 : d) + 1, INT64_MAX);
+      case 0x23: return r.add(f->idx, ft, okey(z ? -0.0 : d), INT64_MAX);
+      default: return r.add(f->idx, ft, okey(z ? -0.0 : d), okey(z ? 0.0 : d));
+    }
+  }
   switch (op) {
-    case 0x20: return k != INT64_MIN && r.add(f->idx, INT64_MIN, k - 1);
-    case 0x21: return r.add(f->idx, INT64_MIN, k);
-    case 0x22: return k != INT64_MAX && r.add(f->idx, k + 1, INT64_MAX);
-    case 0x23: return r.add(f->idx, k, INT64_MAX);
-    default: return r.add(f->idx, k, k);
+    case 0x20: return k != INT64_MIN && r.add(f->idx, ft, INT64_MIN, k - 1);
+    case 0x21: return r.add(f->idx, ft, INT64_MIN, k);
+    case 0x22: return k != INT64_MAX && r.add(f->idx, ft, k + 1, INT64_MAX);
+    case 0x23: return r.add(f->idx, ft, k, INT64_MAX);
+    default: return r.add(f->idx, ft, k, k);
   }
 }
 
@@ -1280,10 +1332,11 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
     }
     // stages were built last -> first; stage index of pattern i: $final=0, p_{m-1}=1, ..., p0=m
     for (int i = 0; i < np; i++) q->stencilProg[i] = d.st[np - i].e[0].prog;
-    // interval fast path: <= 8 stages, every predicate an int range over <= 2 shared columns
+    // interval fast path: <= 8 stages, every predicate a conjunction of ranges over <= 2
+    // shared columns (int, long or double each)
     std::vector<int> ftypes(d.field_type, d.field_type + nf);
     bool range = np <= 8;
-    int cols[2] = {-1, -1}, ncols = 0;
+    int cols[2] = {-1, -1}, ctype[2] = {1, 1}, ncols = 0;
     for (int i = 0; i < np && range; i++) {
       Ranges r;
       if (!ranges_of(ps[i].pred.get(), ftypes, r)) { range = false; break; }
@@ -1294,16 +1347,30 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
         if (slot < 0) {
           if (ncols == 2) { range = false; break; }
           cols[ncols] = r.field[x];
+          ctype[ncols] = r.type[x];
           slot = ncols++;
         }
         q->rangeLo[i][slot] = r.lo[x];
         q->rangeHi[i][slot] = r.hi[x];
       }
     }
+    // a mixed pair is (4-byte, 8-byte): the typed mask kernels are instantiated by width
+    // (stencil.hip launch_m)
+    if (range && ncols == 2 && ctype[0] != 1 && ctype[1] == 1) {
+      std::swap(cols[0], cols[1]);
+      std::swap(ctype[0], ctype[1]);
+      for (int i = 0; i < np; i++) {
+        std::swap(q->rangeLo[i][0], q->rangeLo[i][1]);
+        std::swap(q->rangeHi[i][0], q->rangeHi[i][1]);
+      }
+    }
     q->stencilRange = range;
     q->nRangeCols = ncols == 0 ? 1 : ncols;
     q->rangeCols[0] = cols[0] < 0 ? 0 : cols[0];
     q->rangeCols[1] = cols[1] < 0 ? q->rangeCols[0] : cols[1];
+    // (no column constrained: column 0 read as ints, every value accepted)
+    q->rangeType[0] = (uint8_t)ctype[0];
+    q->rangeType[1] = ncols < 2 ? q->rangeType[0] : (uint8_t)ctype[1];
   } else {
     q->info.kind = CEP_KIND_NFA;
     q->info.arity = 0;

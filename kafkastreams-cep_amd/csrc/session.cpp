@@ -374,7 +374,11 @@ void run_stencil(cep_session* s, QueryRt& r) {
   a.cols = s->cols;
   a.ts = s->ts;
   const bool range = q->stencilRange;
-  for (int c = 0; c < 2; c++) a.col[c] = (const int32_t*)s->cols.p[q->rangeCols[c]];
+  for (int c = 0; c < 2; c++) {
+    a.col[c] = s->cols.p[q->rangeCols[c]];
+    a.col_w[c] = q->rangeType[c] == 1 ? 4 : 8;  // launch_stencil picks the typed mask kernel by these
+    a.col_dbl[c] = q->rangeType[c] == 3;
+  }
   a.aligned = ((uintptr_t)a.col[0] % 16 == 0) && ((uintptr_t)a.col[1] % 16 == 0);
   for (uint32_t i = 0; i < m && i < (uint32_t)kMaxStencil; i++) {
     a.prog[i] = q->stencilProg[i];
@@ -998,6 +1002,20 @@ int cep_query_group_plan(const cep_query* const* queries, int n_queries, int gro
   if (members) *members = mem.data();
   if (n_literals) *n_literals = plan.nkc;
   if (literals) *literals = plan.table.data();
+  return CEP_OK;
+}
+
+int cep_query_stencil_plan(const cep_query* q, cep_stencil_plan* out) {
+  if (!q || !out) return fail(CEP_E_INVALID, "bad argument");
+  if (q->info.kind != CEP_KIND_STENCIL) return fail(CEP_E_INVALID, "not a stencil query");
+  *out = cep_stencil_plan{};
+  if (!q->stencilRange) return CEP_OK;
+  out->range = 1;
+  out->n_cols = (uint32_t)q->nRangeCols;
+  for (int c = 0; c < q->nRangeCols; c++) {
+    out->col_field[c] = (uint32_t)q->rangeCols[c];
+    out->col_type[c] = q->rangeType[c];
+  }
   return CEP_OK;
 }
 

@@ -105,8 +105,32 @@ __device__ __forceinline__ uint64_t spread4(uint32_t x16) {
 // ballot words and the windows are ANDs of shifted words (stage s sits M-1-s events back).
 constexpr int kStSteps = kStWave / 256;               // 16 load steps per wave
 
-template <int M, bool RANGE, int NCOL>
+// An evaluator (StEval: int columns and interpreted predicates; StEvalT: columns that are not
+// all int) gives wave_mask the column-typed parts of the mask phase: Ld, a lane's 4 events of a
+// step as loaded; Cur, the wave's load cursor; keys(), what the stages compare; ballot4(); and
+// for the slow routes Sd, one event's values (load1), range() and slow4().
+template <int M, bool RANGE_, int NCOL>
 struct StEval {
+  static constexpr int STAGES = M;
+  static constexpr bool RANGE = RANGE_;
+  struct Ld {
+    v4i x, y;
+  };
+  struct Sd {
+    int32_t x0, x1;
+  };
+  struct Cur {
+    const v4i *c0, *c1;
+    __device__ __forceinline__ Cur(const StencilArgs& A, uint64_t wbase, int lane)
+        : c0(reinterpret_cast<const v4i*>(static_cast<const int32_t*>(A.col[0]) + wbase) + lane),
+          c1(reinterpret_cast<const v4i*>(static_cast<const int32_t*>(A.col[NCOL - 1]) + wbase) + lane) {}
+    __device__ __forceinline__ Ld load(int q) const {
+      Ld d;
+      d.x = __builtin_nontemporal_load(c0 + q * 64);
+      d.y = NCOL > 1 ? __builtin_nontemporal_load(c1 + q * 64) : d.x;
+      return d;
+    }
+  };
   int32_t lo[M][2], hi[M][2];
   uint32_t span[M][2];
   bool never = false;  // an empty range: no stage-s event, no match (the slow path handles it)
@@ -158,10 +182,32 @@ struct StEval {
       W[3] = __builtin_amdgcn_ballot_w64(in1(s, 0, x.w)) & __builtin_amdgcn_ballot_w64(in1(s, 1, y.w));
     }
   }
+  __device__ __forceinline__ const Ld& keys(const Ld& d) const { return d; }
+  __device__ __forceinline__ void ballot4(int s, const Ld& d, uint64_t* W) const { ballot4(s, d.x, d.y, W); }
+  __device__ __forceinline__ Sd load1(const StencilArgs& A, uint64_t p) const {
+    return Sd{static_cast<const int32_t*>(A.col[0])[p], static_cast<const int32_t*>(A.col[NCOL - 1])[p]};
+  }
+  __device__ __forceinline__ void range(const Sd& v, uint32_t* P, int bit) const { range(v.x0, v.x1, P, bit); }
+  // the 4 events from e0 of a step off the fast path into bits 0..3 of P[s]
+  __device__ __forceinline__ void slow4(const StencilArgs& A, uint64_t e0, uint32_t* P) const {
+    if (RANGE && A.aligned && e0 + 4 <= A.n_events) {
+      const v4i xs = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(static_cast<const int32_t*>(A.col[0]) + e0));
+      v4i ys = xs;
+      if (NCOL > 1)
+        ys = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(static_cast<const int32_t*>(A.col[1]) + e0));
+      range(xs.x, ys.x, P, 0);
+      range(xs.y, ys.y, P, 1);
+      range(xs.z, ys.z, P, 2);
+      range(xs.w, ys.w, P, 3);
+    } else if (e0 < A.n_events) {  // events past the end stay 0: no window can end there
+#pragma unroll
+      for (int i = 0; i < 4; i++) one(A, e0 + i, P, i);
+    }
+  }
   __device__ __forceinline__ void one(const StencilArgs& A, uint64_t p, uint32_t* P, int bit) const {
     if (p >= A.n_events) return;
     if (RANGE) {
-      range(A.col[0][p], A.col[NCOL - 1][p], P, bit);
+      range(load1(A, p), P, bit);
     } else {
       EvalIn in{&A.cols, A.q->field_type, A.ts, p, nullptr, 0, 0, true};
       for (int s = 0; s < M; s++) {
@@ -170,6 +216,159 @@ struct StEval {
         if (interp(A.code, A.prog[s], in, &rn, &ee) != 0) P[s] |= 1u << bit;  // total: never throws
       }
     }
+  }
+};
+
+// The typed range evaluator: one or two columns of W0 and W1 bytes an event (W1 = 0: one
+// column), {8}, {4, 8} or {8, 8} - a long or a double column each 8, told apart by the
+// wave-uniform A.col_dbl alone.  A lane keeps the int path's events 4l..4l+3 of a step, so an
+// 8-byte column is two 16-B loads per lane (32 contiguous bytes: each instruction covers every
+// other 16 B of the step's 2 KiB, the pair all of it), a mixed pair shares one ballot layout,
+// and everything after the ballots is wave_mask's own.  An 8-byte value becomes its order key
+// on load (stencil_args.h RangeStage; a long is its own key) and a stage is, as for ints, one
+// subtract and one unsigned compare: (uint64)(key - lo) <= (uint64)(hi - lo).
+template <int W>
+struct ColLd {};  // a lane's 4 events of one column, as loaded
+template <>
+struct ColLd<4> {
+  v4i a;
+};
+template <>
+struct ColLd<8> {
+  v4i a, b;  // events 4l, 4l+1 | 4l+2, 4l+3 (low word first)
+};
+template <int W>
+struct ColKey {};  // the same as the stages compare them
+template <>
+struct ColKey<4> {
+  v4i v;
+};
+template <>
+struct ColKey<8> {
+  uint64_t k[4];
+};
+
+template <int M, int W0, int W1>
+struct StEvalT {
+  static_assert(W1 == 0 || W1 == 8, "a mixed pair is (4, 8)");
+  static_assert((W0 == 4 && W1 == 8) || W0 == 8, "two int columns: StEval");
+  static constexpr int STAGES = M;
+  static constexpr bool RANGE = true;
+  static constexpr int NCOL = W1 ? 2 : 1;
+  struct Ld {
+    ColLd<W0> x;
+    ColLd<W1> y;
+  };
+  struct Key {
+    ColKey<W0> x;
+    ColKey<W1> y;
+  };
+  struct Sd {
+    uint64_t v[2];  // raw bits (a 4-byte value: the low word)
+  };
+  template <int W>
+  static __device__ __forceinline__ const v4i* cursor(const void* col, uint64_t wbase, int lane) {
+    if constexpr (W == 4) return reinterpret_cast<const v4i*>(static_cast<const int32_t*>(col) + wbase) + lane;
+    else return reinterpret_cast<const v4i*>(static_cast<const uint64_t*>(col) + wbase) + 2 * lane;
+  }
+  template <int W>
+  static __device__ __forceinline__ void load_col(const v4i* c, int q, ColLd<W>& d) {
+    if constexpr (W == 4) {
+      d.a = __builtin_nontemporal_load(c + q * 64);
+    } else if constexpr (W == 8) {
+      d.a = __builtin_nontemporal_load(c + q * 128);
+      d.b = __builtin_nontemporal_load(c + q * 128 + 1);
+    }
+  }
+  struct Cur {
+    const v4i *c0, *c1;
+    __device__ __forceinline__ Cur(const StencilArgs& A, uint64_t wbase, int lane)
+        : c0(cursor<W0>(A.col[0], wbase, lane)), c1(cursor<8>(A.col[NCOL - 1], wbase, lane)) {}
+    __device__ __forceinline__ Ld load(int q) const {
+      Ld d;
+      load_col<W0>(c0, q, d.x);
+      load_col<W1>(c1, q, d.y);
+      return d;
+    }
+  };
+  int32_t lo4[M];  // the 4-byte column (slot 0): int32 bounds, clamped as StEval's
+  uint32_t span4[M];
+  uint64_t lo8[M][2], span8[M][2];
+  uint64_t dmask[2];  // INT64_MAX: a double column (okey flips a negative value's magnitude bits)
+  bool never = false;  // an empty range: no match (range() says so; the spans of one wrap)
+  __device__ __forceinline__ explicit StEvalT(const StencilArgs& A) {
+#pragma unroll
+    for (int c = 0; c < 2; c++) dmask[c] = A.col_dbl[c] ? (uint64_t)INT64_MAX : 0ull;
+#pragma unroll
+    for (int s = 0; s < M; s++)
+#pragma unroll
+      for (int c = 0; c < NCOL; c++) {
+        const int64_t l = A.rs[s].lo[c], h = A.rs[s].hi[c];
+        if (l > h) never = true;
+        if (c == 0 && W0 == 4) {
+          const int32_t l4 = l < INT32_MIN ? INT32_MIN : (l > INT32_MAX ? INT32_MAX : (int32_t)l);
+          const int32_t h4 = h > INT32_MAX ? INT32_MAX : (h < INT32_MIN ? INT32_MIN : (int32_t)h);
+          if (l > INT32_MAX || h < INT32_MIN) never = true;
+          lo4[s] = l4;
+          span4[s] = (uint32_t)h4 - (uint32_t)l4;
+        } else {
+          lo8[s][c] = (uint64_t)l;
+          span8[s][c] = (uint64_t)h - (uint64_t)l;
+        }
+      }
+  }
+  __device__ __forceinline__ uint64_t key(int c, uint64_t bits) const {
+    return bits ^ ((uint64_t)((int64_t)bits >> 63) & dmask[c]);
+  }
+  __device__ __forceinline__ uint64_t key(int c, int lo, int hi) const {
+    return key(c, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+  }
+  __device__ __forceinline__ void keys_col(int, const ColLd<0>&, ColKey<0>&) const {}
+  __device__ __forceinline__ void keys_col(int, const ColLd<4>& d, ColKey<4>& k) const { k.v = d.a; }
+  __device__ __forceinline__ void keys_col(int c, const ColLd<8>& d, ColKey<8>& k) const {
+    k.k[0] = key(c, d.a.x, d.a.y);
+    k.k[1] = key(c, d.a.z, d.a.w);
+    k.k[2] = key(c, d.b.x, d.b.y);
+    k.k[3] = key(c, d.b.z, d.b.w);
+  }
+  // once per step, not per stage
+  __device__ __forceinline__ Key keys(const Ld& d) const {
+    Key k;
+    keys_col(0, d.x, k.x);
+    keys_col(1, d.y, k.y);
+    return k;
+  }
+  __device__ __forceinline__ bool in4(int s, uint32_t v) const { return v - (uint32_t)lo4[s] <= span4[s]; }
+  __device__ __forceinline__ bool in8(int s, int c, uint64_t k) const { return k - lo8[s][c] <= span8[s][c]; }
+  __device__ __forceinline__ bool in(int s, int, const ColKey<4>& k, int e) const { return in4(s, (uint32_t)k.v[e]); }
+  __device__ __forceinline__ bool in(int s, int c, const ColKey<8>& k, int e) const { return in8(s, c, k.k[e]); }
+  __device__ __forceinline__ void ballot4(int s, const Key& k, uint64_t* W) const {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      W[e] = __builtin_amdgcn_ballot_w64(in(s, 0, k.x, e));
+      if constexpr (NCOL > 1) W[e] &= __builtin_amdgcn_ballot_w64(in(s, 1, k.y, e));
+    }
+  }
+  // The slow routes (the tail chunk, unaligned columns, an empty stage, the seed events):
+  // one event at a time, the same compares
+  __device__ __forceinline__ Sd load1(const StencilArgs& A, uint64_t p) const {
+    Sd v;
+    v.v[0] = W0 == 4 ? static_cast<const uint32_t*>(A.col[0])[p] : static_cast<const uint64_t*>(A.col[0])[p];
+    v.v[1] = NCOL > 1 ? static_cast<const uint64_t*>(A.col[1])[p] : 0;
+    return v;
+  }
+  __device__ __forceinline__ void range(const Sd& v, uint32_t* P, int bit) const {
+#pragma unroll
+    for (int s = 0; s < M; s++) {
+      bool ok = !never && (W0 == 4 ? in4(s, (uint32_t)v.v[0]) : in8(s, 0, key(0, v.v[0])));
+      if (NCOL > 1) ok = ok && in8(s, 1, key(1, v.v[1]));
+      P[s] |= (ok ? 1u : 0u) << bit;
+    }
+  }
+  __device__ __forceinline__ void slow4(const StencilArgs& A, uint64_t e0, uint32_t* P) const {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      if (e0 + i < A.n_events) range(load1(A, e0 + i), P, i);
   }
 };
 
@@ -188,20 +387,19 @@ struct WaveMask {
 // windows crossing a key start are settled after the loop, on the natural words, with vector
 // work.  (This keeps the loop's scalar registers down - 58 instead of 106, 8 waves per SIMD
 // instead of 6 - and the pass at ~75 us for 1e8 events instead of ~90: profiles/r05/.)
-template <int M, bool RANGE, int NCOL>
+template <class EV>
 __device__ __forceinline__ void wave_mask(const StencilArgs& A, const uint64_t wbase, const int lane, WaveMask& out) {
+  constexpr int M = EV::STAGES;
+  constexpr bool RANGE = EV::RANGE;
   constexpr int H = M - 1;              // events a window reaches back
-  const StEval<M, RANGE, NCOL> ev(A);
+  using Ld = typename EV::Ld;
+  const EV ev(A);
   const bool fast = RANGE && A.aligned && wbase + kStWave <= A.n_events && !ev.never;
   // The fast path's first step is requested before anything else: the key-start words and
   // the seed events below are dependent round trips
-  const v4i* c0 = reinterpret_cast<const v4i*>(A.col[0] + wbase) + lane;
-  const v4i* c1 = reinterpret_cast<const v4i*>(A.col[NCOL - 1] + wbase) + lane;
-  v4i xa = {0, 0, 0, 0}, ya = {0, 0, 0, 0};
-  if (fast) {
-    xa = __builtin_nontemporal_load(c0);
-    ya = NCOL > 1 ? __builtin_nontemporal_load(c1) : xa;
-  }
+  const typename EV::Cur cur(A, wbase, lane);
+  Ld la{};
+  if (fast) la = cur.load(0);
   // the key holding the wave's first event (wave_keys)
   const uint64_t n_waves = (A.n_events + kStWave - 1) / kStWave;  // n_events >= 1: the tile exists
   const uint64_t wi = wbase / kStWave;
@@ -210,11 +408,8 @@ __device__ __forceinline__ void wave_mask(const StencilArgs& A, const uint64_t w
   // ending at the wave's first H events, settled after the loop
   const int64_t sp = (int64_t)wbase - H + lane;
   const bool sv = H > 0 && lane < 2 * H && sp >= 0 && (uint64_t)sp < A.n_events;
-  int32_t sx0 = 0, sx1 = 0;
-  if (RANGE && sv) {
-    sx0 = A.col[0][sp];
-    sx1 = A.col[NCOL - 1][sp];
-  }
+  typename EV::Sd sd{};
+  if (RANGE && sv) sd = ev.load1(A, (uint64_t)sp);
   // Key starts in [wbase - 8, wend): lanes read key_off[k0 - 8 + 64 c + lane] (the 8 keys
   // before k0 may start among the 8 events before the wave) and a wave-uniform loop visits
   // the starts in range, in key order.  bw: this lane's start bits, pkb: starts among the 8
@@ -265,32 +460,22 @@ __device__ __forceinline__ void wave_mask(const StencilArgs& A, const uint64_t w
 #pragma unroll
     for (int k = 0; k < 4; k++) pW[s][k] = 0;
   uint64_t myword = 0;  // ballot layout: word k of step q for lane 4q + k
-  // step q of the wave: x/y hold its 4 events per lane on the fast path (FAST: a
+  // step q of the wave: x holds its 4 events per lane on the fast path (FAST: a
   // std::integral_constant, so each loop below gets its own straight-line body)
-  auto step = [&](const int q, const v4i x, const v4i y, auto fast_c) {
+  auto step = [&](const int q, const Ld& x, auto fast_c) {
     constexpr bool FAST = decltype(fast_c)::value;
     const uint64_t e0 = wbase + (uint64_t)q * 256 + (uint64_t)lane * 4;
     // stage words of this step (wave-uniform, scalar registers)
     uint64_t W[M][4];
     if (FAST) {
+      const auto& k = ev.keys(x);
 #pragma unroll
-      for (int s = 0; s < M; s++) ev.ballot4(s, x, y, W[s]);
+      for (int s = 0; s < M; s++) ev.ballot4(s, k, W[s]);
     } else {
       uint32_t P[M];
 #pragma unroll
       for (int s = 0; s < M; s++) P[s] = 0;
-      if (RANGE && A.aligned && e0 + 4 <= A.n_events) {
-        const v4i xs = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(A.col[0] + e0));
-        v4i ys = xs;
-        if (NCOL > 1) ys = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(A.col[1] + e0));
-        ev.range(xs.x, ys.x, P, 0);
-        ev.range(xs.y, ys.y, P, 1);
-        ev.range(xs.z, ys.z, P, 2);
-        ev.range(xs.w, ys.w, P, 3);
-      } else if (e0 < A.n_events) {  // events past the end stay 0: no window can end there
-#pragma unroll
-        for (int i = 0; i < 4; i++) ev.one(A, e0 + i, P, i);
-      }
+      ev.slow4(A, e0, P);
 #pragma unroll
       for (int s = 0; s < M; s++)
 #pragma unroll
@@ -325,20 +510,18 @@ __device__ __forceinline__ void wave_mask(const StencilArgs& A, const uint64_t w
     // two one-step buffers: while one step computes, the other's load is in flight.  The
     // loads are unconditional (the last pair re-reads its own step): a load under a branch
     // makes the waitcnt pass drain every outstanding load before the first use.
-    v4i xb, yb;
+    Ld lb;
 #pragma unroll 1
     for (int q = 0; q < kStSteps; q += 2) {
-      xb = __builtin_nontemporal_load(c0 + (q + 1) * 64);
-      yb = NCOL > 1 ? __builtin_nontemporal_load(c1 + (q + 1) * 64) : xb;
-      step(q, xa, ya, std::true_type{});
+      lb = cur.load(q + 1);
+      step(q, la, std::true_type{});
       const int qn = q + 2 < kStSteps ? q + 2 : q;
-      xa = __builtin_nontemporal_load(c0 + qn * 64);
-      ya = NCOL > 1 ? __builtin_nontemporal_load(c1 + qn * 64) : xa;
-      step(q + 1, xb, yb, std::true_type{});
+      la = cur.load(qn);
+      step(q + 1, lb, std::true_type{});
     }
   } else {
-    const v4i z = {0, 0, 0, 0};
-    for (int q = 0; q < kStSteps; q++) step(q, z, z, std::false_type{});
+    const Ld z{};
+    for (int q = 0; q < kStSteps; q++) step(q, z, std::false_type{});
   }
   // natural words: events wbase + 256 q + 64 r + i (q = lane / 4, r = lane % 4) are bits
   // 16 r .. 16 r + 15 of the ballot words of step q, held by lanes 4q .. 4q + 3
@@ -359,7 +542,7 @@ __device__ __forceinline__ void wave_mask(const StencilArgs& A, const uint64_t w
 #pragma unroll
     for (int s = 0; s < M; s++) P[s] = 0;
     if (sv) {
-      if constexpr (RANGE) ev.range(sx0, sx1, P, 0);
+      if constexpr (RANGE) ev.range(sd, P, 0);
       else ev.one(A, (uint64_t)sp, P, 0);
     }
     uint64_t seed = wbase >= (uint64_t)H ? (1ull << H) - 1ull : 0ull;
@@ -397,8 +580,8 @@ constexpr uint64_t kStGroupChunks = kEmW * (kStTile / kStWave);  // chunks per g
 // counters of 256 waves 156).  (A launch of resident waves looping over the chunks, so a
 // chunk's stores overlap the next chunk's loads, measured 142 us: the loop's scalar state spills.)
 
-template <int M, bool RANGE, int NCOL>
-__global__ void __launch_bounds__(kStThreads) stencil_mask(StencilArgs A) {
+template <class EV>
+__device__ __forceinline__ void mask_chunk(const StencilArgs& A) {
   // wv through readfirstlane: the compiler cannot see that threadIdx.x >> 6 is wave-uniform,
   // and everything derived from it (the fast-path branch, the ballot words) would go to VGPRs
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -406,7 +589,7 @@ __global__ void __launch_bounds__(kStThreads) stencil_mask(StencilArgs A) {
   if (chunk >= A.n_chunk) return;  // (wave-uniform; no barrier below)
   const uint64_t wbase = chunk * kStWave;
   WaveMask o;
-  wave_mask<M, RANGE, NCOL>(A, wbase, lane, o);
+  wave_mask<EV>(A, wbase, lane, o);
   const uint64_t ws = wbase + (uint64_t)lane * 64;
   // (bit 31: a key starts inside the word after its first event - stencil_emit walks key_off
   // there; elsewhere a match's sequence number is word_seq + its offset in the word)
@@ -418,6 +601,17 @@ __global__ void __launch_bounds__(kStThreads) stencil_mask(StencilArgs A) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
   if (lane == 0 && cnt) atomicAdd(A.group_cnt + chunk / kStGroupChunks, cnt);  // (no return value)
+}
+
+template <int M, bool RANGE, int NCOL>
+__global__ void __launch_bounds__(kStThreads) stencil_mask(StencilArgs A) {
+  mask_chunk<StEval<M, RANGE, NCOL>>(A);
+}
+
+// The typed variant: columns of W0 (and W1) bytes an event, not all int (StEvalT)
+template <int M, int W0, int W1>
+__global__ void __launch_bounds__(kStThreads) stencil_mask_typed(StencilArgs A) {
+  mask_chunk<StEvalT<M, W0, W1>>(A);
 }
 
 // Pass 2: a thread per kEmW consecutive 64-event words (a block: kEmW mask tiles), the block's
@@ -554,22 +748,30 @@ hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n
 
 uint64_t stencil_waves(uint64_t n_events) { return (n_events + kStWave - 1) / kStWave; }
 
-template <int M, bool RANGE, int NCOL>
-static hipError_t launch_one(const StencilArgs& a, uint64_t n_tiles, hipStream_t st) {
+// the mask kernel `mask` (an int32 or a typed instantiation for M stages), then the emit pass
+template <int M>
+static hipError_t launch_one(void (*mask)(StencilArgs), const StencilArgs& a, uint64_t n_tiles, hipStream_t st) {
   // (a separate build for the whole fast-path chunks, without the slow path's code and
   // registers, measured the same - 79.5 against 79.6 us for 1e8 events - and cost a launch)
   StencilArgs b = a;
   b.n_chunk = (a.n_events + kStWave - 1) / kStWave;
-  hipLaunchKernelGGL((stencil_mask<M, RANGE, NCOL>), dim3((uint32_t)((b.n_chunk + 3) / 4)), dim3(kStThreads), 0, st, b);
+  hipLaunchKernelGGL(mask, dim3((uint32_t)((b.n_chunk + 3) / 4)), dim3(kStThreads), 0, st, b);
   hipLaunchKernelGGL(stencil_emit<M>, dim3((uint32_t)((n_tiles + kEmW - 1) / kEmW)), dim3(kStThreads), 0, st, a);
   return hipGetLastError();
 }
 
+// The mask kernel by the widths of the range columns (StencilArgs.col_w): all int, the int32
+// instantiations; any other, the typed ones
 template <int M>
 static hipError_t launch_m(const StencilArgs& a, bool range, int ncol, uint64_t n_tiles, hipStream_t st) {
-  if (range && ncol == 1) return launch_one<M, true, 1>(a, n_tiles, st);
-  if (range) return launch_one<M, true, 2>(a, n_tiles, st);
-  return launch_one<M, false, 1>(a, n_tiles, st);
+  if (!range) return launch_one<M>(stencil_mask<M, false, 1>, a, n_tiles, st);
+  const int w0 = a.col_w[0], w1 = ncol > 1 ? a.col_w[1] : 0;
+  if (w0 == 4 && w1 == 0) return launch_one<M>(stencil_mask<M, true, 1>, a, n_tiles, st);
+  if (w0 == 4 && w1 == 4) return launch_one<M>(stencil_mask<M, true, 2>, a, n_tiles, st);
+  if (w0 == 8 && w1 == 0) return launch_one<M>(stencil_mask_typed<M, 8, 0>, a, n_tiles, st);
+  if (w0 == 4 && w1 == 8) return launch_one<M>(stencil_mask_typed<M, 4, 8>, a, n_tiles, st);
+  if (w0 == 8 && w1 == 8) return launch_one<M>(stencil_mask_typed<M, 8, 8>, a, n_tiles, st);
+  return hipErrorInvalidValue;  // (compile.cpp orders a mixed pair (4, 8))
 }
 
 hipError_t launch_stencil(int m, const StencilArgs& a, bool range, int ncol, hipStream_t st) {

@@ -5,7 +5,14 @@
 
 namespace cep {
 
-struct RangeStage {  // conjunction of lo <= col_c <= hi for c in {0, 1}
+// conjunction of lo <= col_c <= hi for c in {0, 1}, as int64 in the column's order: an int or a
+// long as itself, a double as its order key okey(bits) = bits ^ ((bits >> 63) & INT64_MAX)
+// (signed compare of keys = IEEE compare of the doubles, -0.0 and +0.0 adjacent keys -1 and 0,
+// NaNs beyond okey(-inf) and okey(+inf)).  That is the unsigned key `bits ^ ((bits >> 63) |
+// 2^63)` less 2^63: the kernel tests (uint64)(key - lo) <= (uint64)(hi - lo), where the 2^63
+// cancels.  A constrained double side is clamped to the infinities' keys by compile.cpp (a NaN
+// fails); INT64_MIN .. INT64_MAX accepts every value, NaN included.
+struct RangeStage {
   int64_t lo[2], hi[2];
 };
 
@@ -13,7 +20,9 @@ struct StencilArgs {
   uint64_t n_keys, n_events;
   const uint64_t* key_off;
   const uint32_t* wave_key;  // key holding the first event of each wave's span (kStWave events)
-  const int32_t* col[2];     // range fast path: up to two int columns
+  const void* col[2];        // range fast path: up to two columns, of
+  uint8_t col_w[2];          // 4 (int) or 8 bytes (long, double) an event; a mixed pair is (4, 8)
+  bool col_dbl[2];           // a double column: its values compare by their order key
   RangeStage rs[8];
   // generic path (interpreted predicates)
   const DevQuery* q;

@@ -31,7 +31,7 @@ EXPORTS = [
     "cep_batch_layout", "cep_session_snapshot", "cep_session_restore",
     "cep_decode_stock_json", "cep_jit_precompile_group", "cep_query_group_plan",
     "cep_last_stats", "cep_gather_keys", "cep_timing_totals", "cep_symbol_keys", "cep_lane_balance",
-    "cep_decode_json",
+    "cep_decode_json", "cep_query_stencil_plan",
 ]
 # every symbol include/cep_synth.h declares (the generator library of the bench and tests)
 SYNTH_EXPORTS = ["cep_synth_last_error", "cep_synth_count", "cep_synth_generate", "cep_synth_generate_arrival",
@@ -42,6 +42,11 @@ class QueryInfo(C.Structure):
     _fields_ = [("n_patterns", C.c_uint32), ("n_stages", C.c_uint32), ("n_names", C.c_uint32),
                 ("n_fields", C.c_uint32), ("n_states", C.c_uint32), ("kind", C.c_uint32),
                 ("arity", C.c_uint32), ("compile_error", C.c_int32)]
+
+
+class StencilPlan(C.Structure):
+    _fields_ = [("range", C.c_uint32), ("n_cols", C.c_uint32), ("col_field", C.c_uint32 * 2),
+                ("col_type", C.c_uint8 * 2)]
 
 
 class Opts(C.Structure):
@@ -95,6 +100,7 @@ def lib():
             "cep_query_group_plan": ([C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(u32),
                                       C.POINTER(C.POINTER(i32)), C.POINTER(u32), C.POINTER(C.POINTER(C.c_int64))],
                                      C.c_int),
+            "cep_query_stencil_plan": ([vp, C.POINTER(StencilPlan)], C.c_int),
             "cep_session_create": ([C.POINTER(vp), C.c_int, C.POINTER(Opts), C.POINTER(vp)], C.c_int),
             "cep_session_destroy": ([vp], None),
             "cep_push_batch": ([vp, C.POINTER(Batch)], C.c_int),
@@ -192,6 +198,15 @@ class Query:
     @property
     def jit_source(self) -> str:
         return lib().cep_query_jit_source(self.h).decode()
+
+    def stencil_plan(self) -> dict:
+        """How stencil_mask reads a CEP_KIND_STENCIL query's events (cep_query_stencil_plan):
+        {range, n_cols, col_field, col_type}; col_type holds IR type codes (1 int, 2 long,
+        3 double).  Raises CepError for a CEP_KIND_NFA query."""
+        p = StencilPlan()
+        _check(lib().cep_query_stencil_plan(self.h, C.byref(p)))
+        return {"range": p.range, "n_cols": p.n_cols, "col_field": list(p.col_field[:p.n_cols]),
+                "col_type": list(p.col_type[:p.n_cols])}
 
     def precompile(self) -> float:
         """Compile the JIT kernel into the code-object cache (no GPU needed); seconds spent."""

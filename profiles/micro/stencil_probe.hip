@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(256) v2(StencilArgs A, uint64_t* out) {
   const uint64_t wbase = ((uint64_t)blockIdx.x * 4 + wv) * (uint64_t)SPW * 256;
   const StEval<M, true, 1> ev(A);
   if (wbase + (uint64_t)SPW * 256 > A.n_events) return;  // (probe: whole waves only)
-  const v4i* c0 = reinterpret_cast<const v4i*>(A.col[0] + wbase) + lane;
+  const v4i* c0 = reinterpret_cast<const v4i*>(static_cast<const int32_t*>(A.col[0]) + wbase) + lane;
   v4i xa[PF], xb[PF];
 #pragma unroll
   for (int d = 0; d < PF; d++) xa[d] = __builtin_nontemporal_load(c0 + d * 64);
