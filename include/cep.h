@@ -145,14 +145,17 @@ int cep_query_stencil_plan(const cep_query* q, cep_stencil_plan* out);  /* CEP_E
 
 typedef struct {
   int device;             /* HIP device ordinal */
-  int force_nfa;          /* 1: run CEP_KIND_STENCIL queries on the general NFA kernel */
+  int force_nfa;          /* 1: run CEP_KIND_STENCIL queries on the general NFA kernel (per-batch
+                             and streaming sessions alike) */
   int tier;               /* CEP_TIER_JIT (default) or CEP_TIER_INTERP */
   uint32_t max_runs;      /* live runs per key (0 = default 32); retried x8 on overflow */
   double pool_factor;     /* buffer pool size per event of the batch (0 = default) */
   int streaming;          /* 1: a key's NFA state carries over from one batch to the next (its
                              events in consecutive batches are one stream, sequence numbers
                              continue; every batch has the same n_keys); 0: every batch starts
-                             every key from the initial state */
+                             every key from the initial state.  CEP_KIND_STENCIL queries stay on
+                             the stencil: a key carries one word (its event count and which
+                             prefixes of the chain its last events satisfy) */
   int no_groups;          /* 1: every NFA query runs its own launch.  0 (default): in a per-batch
                              JIT session, queries that differ only in literal values (config 5's
                              64 variants) run as one kernel launch, lanes = (query, key), reading
@@ -189,8 +192,10 @@ typedef struct {
  * previous batch left it (run queue, shared buffer, folds, sequence numbers); otherwise every
  * batch starts every key from the NFA's initial state.  A streaming session cannot re-run a
  * key: one that hits a limit (CEP_KEY_CAPACITY: size max_runs for the query) stops there,
- * like a key whose query threw; its buffer walks run in place (no CEP_KEY_CONFLICT), and
- * stencil-kind queries run on the NFA kernel.
+ * like a key whose query threw; its buffer walks run in place (no CEP_KEY_CONFLICT).
+ * Stencil-kind queries run the stencil there too (unless cep_opts.force_nfa): stencil_mask,
+ * stencil_edge - the windows that begin in an earlier batch, from a per-key carry word - and
+ * stencil_emit, asynchronously as in a per-batch session; they have no limits and no errors.
  * Buffer lifetime.  CEP_MEM_HOST batches are copied to the device before the call returns:
  * their buffers are borrowed for the call only.  CEP_MEM_DEVICE batches are read in place:
  * NFA batches finish before the call returns, but stencil-kind queries and the watermark
@@ -251,7 +256,8 @@ int cep_watermark(cep_session* s, int64_t* out);
 
 /* Device time of the last batch, per query, from HIP events recorded on the session
  * stream (ms): the matching kernel launches (kernel_ms, `launches` of them: the NFA kernel
- * incl. capacity retries, or stencil_mask + stencil_emit) and the
+ * incl. capacity retries, or stencil_mask + stencil_emit, in a streaming session with
+ * stencil_edge between them: 3) and the
  * setup/compaction kernels (aux_ms; 0 for a stencil batch, whose 4 us key-index pass is left
  * unbracketed: an event marker costs the stream about as much). */
 /* ---- streaming-session snapshot / restore ----
@@ -263,14 +269,20 @@ int cep_watermark(cep_session* s, int64_t* out);
  * of at least that size it writes the blob (the session is unchanged).  cep_session_restore
  * loads a blob into a streaming session created over the same queries and max_runs; the
  * next cep_push_batch continues every key's stream where the snapshot left it.  Blobs from
- * other queries, options or versions are rejected with CEP_E_INVALID before any change. */
+ * other queries, options or versions are rejected with CEP_E_INVALID before any change.
+ * A stencil-kind query's state is its carry array alone (8 bytes a key); a blob holding NFA
+ * state for it (a force_nfa session's, or one written when streams ran such queries on the
+ * NFA kernel) is rejected in the same way, and so is a carry array for a force_nfa session. */
 int cep_session_snapshot(cep_session* s, void* buf, size_t cap, size_t* size);
 
 /* Streaming sessions: floor[k] = the smallest sequence number of key k's events that a live
  * node of the query's shared buffer still holds (0xFFFFFFFF: none) - the only events a later
  * match of the key can contain (KVSharedVersionedBuffer.java:143-171 deletes a node when its
  * last reference is walked).  A host that keeps records to build Sequences may drop the older
- * ones.  floor is host memory [n_keys]; n_keys <= the session's key space. */
+ * ones.  floor is host memory [n_keys]; n_keys <= the session's key space.
+ * A stencil-kind query has no buffer: its floor comes from the carry word, the key's event
+ * count less the length of its longest waiting run (live bit t: a run of the last t + 1
+ * events), 0xFFFFFFFF when no run waits - exact, so never below the NFA path's floor. */
 int cep_live_floor(cep_session* s, int query, uint32_t* floor, uint64_t n_keys);
 int cep_session_restore(cep_session* s, const void* buf, size_t size);
 

@@ -194,6 +194,12 @@ struct QueryRt {
   bool tev_used[kRing] = {};
   int tev_next = 0, tev_last = -1;
   uint64_t ks_zeroed = 0;  // stencil: KeyState entries known zero
+  // a streaming session's stencil query: a word per key (count << 32 | live, stencil.hip
+  // stencil_edge).  A batch reads sc_carry[sc_cur] and writes the other; they swap after it
+  DBuf sc_carry[2];
+  int sc_cur = 0;
+  uint64_t sc_keys = 0;
+  bool sc_init = false;
   // every batch's timing since the last cep_timing_totals reset
   double acc_kernel_ms = 0, acc_aux_ms = 0;
   uint64_t acc_batches = 0;
@@ -330,7 +336,18 @@ void resolve(cep_session* s) {
   }
 }
 
-// Strict chains (stencil.hip): wave_keys, stencil_mask, stencil_emit; no host sync.
+// a streaming session's carry arrays for n_keys keys (zero: every key in the initial state)
+void stencil_carry_init(cep_session* s, QueryRt& r, uint64_t n_keys) {
+  const uint64_t bytes = sizeof(uint64_t) * std::max<uint64_t>(n_keys, 1);
+  for (auto& c : r.sc_carry) c.ensure(bytes);
+  r.sc_cur = 0;
+  r.sc_keys = n_keys;
+  HIPCHECK(hipMemsetAsync(r.sc_carry[0].p, 0, bytes, s->stream));
+  r.sc_init = true;
+}
+
+// Strict chains (stencil.hip): wave_keys, stencil_mask, stencil_emit; no host sync.  In a
+// streaming session stencil_edge runs between the two with the per-key carry.
 void run_stencil(cep_session* s, QueryRt& r) {
   const cep_query* q = r.q;
   const uint32_t m = q->info.arity;
@@ -397,6 +414,14 @@ void run_stencil(cep_session* s, QueryRt& r) {
   a.overflow = &sc->overflow;
   if (!r.h_sc_dev) HIPCHECK(hipHostGetDevicePointer((void**)&r.h_sc_dev, r.h_sc, 0));
   a.total_host = &r.h_sc_dev->total;  // the emit pass writes the count straight to the host copy
+  const bool streaming = s->opts.streaming != 0;
+  if (streaming) {
+    if (!r.sc_init) stencil_carry_init(s, r, nk);
+    else if (nk != r.sc_keys)
+      throw std::invalid_argument("the batches of a streaming session share one key space (n_keys)");
+    a.carry_prev = r.sc_carry[r.sc_cur].as<uint64_t>();
+    a.carry_next = r.sc_carry[r.sc_cur ^ 1].as<uint64_t>();
+  }
   // No event before wave_keys: every marker packet costs the stream ~5 us between kernels
   // (4 % of this 0.12 ms step), so the 4 us key-index pass is not timed (aux_ms 0).
   // wave_keys also zeroes the counters (no memset launch); no D2H copy of them either
@@ -406,7 +431,8 @@ void run_stencil(cep_session* s, QueryRt& r) {
   HIPCHECK(launch_stencil((int)m, a, range, q->nRangeCols, s->stream));
   HIPCHECK(hipEventRecord(r.tev[slot][2], s->stream));
   r.pending = true;
-  r.launches = 2;  // stencil_mask + stencil_emit
+  r.launches = streaming ? 3 : 2;  // stencil_mask (+ stencil_edge) + stencil_emit
+  if (streaming && s->n_events) r.sc_cur ^= 1;  // (an empty batch launches nothing: the carry stands)
   r.digest_valid = false;
   r.arity = m;
   // no per-key errors on this path: the predicates and folds are total
@@ -1062,7 +1088,7 @@ int cep_session_create(const cep_query* const* queries, int n_queries, const cep
     // literals as one launch (plan_groups); streams and the interpreter run one query each
     std::vector<int> nfa;
     for (int i = 0; i < n_queries; i++)
-      if (queries[i]->info.kind == CEP_KIND_NFA || s->opts.force_nfa || s->opts.streaming) nfa.push_back(i);
+      if (queries[i]->info.kind == CEP_KIND_NFA || s->opts.force_nfa) nfa.push_back(i);
     std::vector<GroupPlan> plans;
     if (s->opts.tier == CEP_TIER_JIT && !s->opts.streaming && !s->opts.no_groups) {
       std::vector<const cep_query*> qv;
@@ -1143,6 +1169,7 @@ int cep_session_reset(cep_session* s) {
     DeviceGuard g(s->device);
     HIPCHECK(hipStreamSynchronize(s->stream));
     for (auto& r : s->qs) {
+      if (r->sc_init) stencil_carry_init(s, *r, r->sc_keys);
       StreamState& S = r->st;
       if (!S.init) continue;
       // KeyCarry.live = 0: each key restarts from the initial state at its next batch (its ring
@@ -1306,7 +1333,7 @@ int cep_push_batch(cep_session* s, const cep_batch* b) {
     const uint64_t claim_slack = (uint64_t)s->cus * 64 * 128;
     if (s->groups.size() && (uint64_t)s->qs.size() * s->n_keys + claim_slack >= 0xFFFFFFFFull)
       throw std::invalid_argument("queries x keys of a batch must stay below 2^32 (job ids are u32)");
-    for (auto& r : s->qs)  // a stream carries NFA state between batches: stencil queries run on the NFA there
+    for (auto& r : s->qs)
       if (r->group < 0) run_stencil(s, *r);
     const double t0 = host_trace() ? now_ms() : 0;
     for (auto& g : s->groups) run_nfa(s, *g);
@@ -1485,12 +1512,16 @@ struct SnapQueryHdr {
   uint64_t fingerprint, n_keys, ring_bytes;
   uint32_t F, rcap, node_used, pred_used, init, pad;
 };
+// SnapQueryHdr.init: 0 no state yet, 1 NFA state (StreamState), kSnapStencil a stencil query's
+// carry array alone (n_keys words).  A query restores only the kind of state its session runs.
+constexpr uint32_t kSnapStencil = 2;
 
 uint64_t snap_size(const cep_session* s) {
   uint64_t n = 32;  // magic, version, n_queries, watermark, reserved
   for (auto& r : s->qs) {
     n += sizeof(SnapQueryHdr);
     const StreamState& S = r->st;
+    if (r->sc_init) n += sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1);
     if (S.init)
       n += sizeof(KeyCarry) * std::max<uint64_t>(S.n_keys, 1) + S.ring_bytes + (sizeof(Node) + sizeof(Pred)) * S.node_used +
            sizeof(Pred) * S.pred_used;
@@ -1521,13 +1552,18 @@ int cep_session_snapshot(cep_session* s, void* buf, size_t cap, size_t* size) {
       const StreamState& S = r->st;
       SnapQueryHdr h{query_fingerprint(r->q), S.n_keys, S.ring_bytes, (uint32_t)r->F, S.rcap,
                      S.node_used, S.pred_used, S.init ? 1u : 0u, 0};
+      if (r->sc_init) {
+        h.n_keys = r->sc_keys;
+        h.init = kSnapStencil;
+      }
       std::memcpy(o, &h, sizeof h);
       o += sizeof h;
-      if (!S.init) continue;
       auto d2h = [&](const void* src, uint64_t n) {
         if (n) copy_sync(o, src, n, hipMemcpyDeviceToHost, s->stream);
         o += n;
       };
+      if (r->sc_init) d2h(r->sc_carry[r->sc_cur].p, sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1));
+      if (!S.init) continue;
       d2h(S.carry.p, sizeof(KeyCarry) * std::max<uint64_t>(S.n_keys, 1));
       d2h(S.rings.p, S.ring_bytes);
       d2h(S.nodes.p, sizeof(Node) * S.node_used);
@@ -1543,8 +1579,19 @@ int cep_live_floor(cep_session* s, int query, uint32_t* floor, uint64_t n_keys) 
   QueryRt& r = *s->qs[query];
   const StreamState& S = r.st;
   if (S.init && n_keys > S.n_keys) return fail(CEP_E_INVALID, "n_keys larger than the session's key space");
+  if (r.sc_init && n_keys > r.sc_keys) return fail(CEP_E_INVALID, "n_keys larger than the session's key space");
   return guarded([&] {
     DeviceGuard g(s->device);
+    if (r.sc_init && n_keys) {
+      // a stencil query's carry says it all: live bit t is a run of the key's last t + 1 events
+      std::vector<uint64_t> c(n_keys);
+      copy_sync(c.data(), r.sc_carry[r.sc_cur].p, sizeof(uint64_t) * n_keys, hipMemcpyDeviceToHost, s->stream);
+      for (uint64_t k = 0; k < n_keys; k++) {
+        const uint32_t live = (uint32_t)c[k], count = (uint32_t)(c[k] >> 32);
+        floor[k] = live ? count - (32u - (uint32_t)__builtin_clz(live)) : 0xFFFFFFFFu;
+      }
+      return;
+    }
     if (!S.init || n_keys == 0) {
       for (uint64_t k = 0; k < n_keys; k++) floor[k] = 0xFFFFFFFFu;
       return;
@@ -1583,6 +1630,14 @@ int cep_session_restore(cep_session* s, const void* buf, size_t size) {
       q += sizeof h;
       if (h.fingerprint != query_fingerprint(r->q)) return fail(CEP_E_INVALID, "snapshot of a different query");
       if (!h.init) continue;
+      if ((h.init == kSnapStencil) != (r->group < 0) || h.init > kSnapStencil)
+        return fail(CEP_E_INVALID, "snapshot holds the query's state for the other path (stencil carry / NFA state)");
+      if (h.init == kSnapStencil) {
+        const uint64_t n = sizeof(uint64_t) * std::max<uint64_t>(h.n_keys, 1);
+        if ((uint64_t)(end - q) < n) return fail(CEP_E_INVALID, "snapshot truncated");
+        q += n;
+        continue;
+      }
       const uint32_t rcap = s->opts.max_runs ? s->opts.max_runs : 32;
       if (h.rcap != rcap || h.F != (uint32_t)r->F || h.ring_bytes != ring_size(r->F, std::max<uint64_t>(h.n_keys, 1), rcap))
         return fail(CEP_E_INVALID, "snapshot taken with other session options (max_runs)");
@@ -1602,7 +1657,15 @@ int cep_session_restore(cep_session* s, const void* buf, size_t size) {
       q += sizeof h;
       StreamState& S = r->st;
       S.init = false;
+      r->sc_init = false;
       if (!h.init) continue;
+      if (h.init == kSnapStencil) {
+        const uint64_t n = sizeof(uint64_t) * std::max<uint64_t>(h.n_keys, 1);
+        stencil_carry_init(s, *r, h.n_keys);
+        copy_sync(r->sc_carry[0].p, q, n, hipMemcpyHostToDevice, s->stream);
+        q += n;
+        continue;
+      }
       auto h2d = [&](DBuf& dst, uint64_t n) {
         dst.ensure(std::max<uint64_t>(n, 16));
         if (n) copy_sync(dst.p, q, n, hipMemcpyHostToDevice, s->stream);

@@ -23,6 +23,8 @@
 // with a decoupled look-back over the tile counts was measured slower: 126.7 us against 112.6
 // for the two passes at round 5's start, profiles/r05/ - a tile waits for every tile before
 // it, ~24 look-back round trips deep within one round of co-resident tiles.)
+// In a streaming session stencil_edge runs between the two passes: a carry word per key settles
+// the windows that begin in an earlier batch (below, "streaming sessions").
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -204,6 +206,8 @@ struct StEval {
       for (int i = 0; i < 4; i++) one(A, e0 + i, P, i);
     }
   }
+  // stencil_edge's dense route: the same (one 16-B load per column where aligned)
+  __device__ __forceinline__ void bits4(const StencilArgs& A, uint64_t e0, uint32_t* P) const { slow4(A, e0, P); }
   __device__ __forceinline__ void one(const StencilArgs& A, uint64_t p, uint32_t* P, int bit) const {
     if (p >= A.n_events) return;
     if (RANGE) {
@@ -369,6 +373,23 @@ struct StEvalT {
 #pragma unroll
     for (int i = 0; i < 4; i++)
       if (e0 + i < A.n_events) range(load1(A, e0 + i), P, i);
+  }
+  // stencil_edge's dense route: 4 whole events from e0 (a multiple of 4) with the fast path's
+  // 16-B loads and compares, the rest as slow4
+  __device__ __forceinline__ void bits4(const StencilArgs& A, uint64_t e0, uint32_t* P) const {
+    if (!A.aligned || e0 + 4 > A.n_events || never) return slow4(A, e0, P);
+    Ld d;
+    load_col<W0>(cursor<W0>(A.col[0], e0, 0), 0, d.x);
+    load_col<W1>(cursor<8>(A.col[NCOL - 1], e0, 0), 0, d.y);
+    const Key k = keys(d);
+#pragma unroll
+    for (int s = 0; s < M; s++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        bool ok = in(s, 0, k.x, e);
+        if constexpr (NCOL > 1) ok = ok && in(s, 1, k.y, e);
+        P[s] |= (ok ? 1u : 0u) << e;
+      }
   }
 };
 
@@ -622,7 +643,10 @@ __global__ void __launch_bounds__(kStThreads) stencil_mask_typed(StencilArgs A) 
 // grid fits the chip in one round.)
 constexpr uint32_t kEmStage = 3072;  // matches staged in LDS (24 KB: 6 blocks per CU)
 
-template <int M>
+//
+// STREAM (streaming sessions): the words hold in-batch sequence numbers; a match's is that plus
+// the events its key had before the batch (carry_prev's count).
+template <int M, bool STREAM>
 __global__ void __launch_bounds__(kStThreads) stencil_emit(StencilArgs A) {
   __shared__ uint32_t s_wsum[kStThreads / 64];
   __shared__ uint64_t s_toff[kStThreads / 64];
@@ -691,19 +715,25 @@ __global__ void __launch_bounds__(kStThreads) stencil_emit(StencilArgs A) {
       kstart = A.key_off[key];
       knext = A.key_off[key + 1];
     }
+    uint32_t base = 0;  // the key's events before this batch
+    if (STREAM) base = (uint32_t)(A.carry_prev[key] >> 32);
     while (match) {
       const int b = __builtin_ctzll(match);
       match &= match - 1;
       const uint64_t p = p0 + b;
       uint32_t seq = ws[i] + (uint32_t)b;
       if (cross) {
+        bool moved = false;
         while (p >= knext) {  // the next key (empty keys share their offset: skipped too)
           key++;
           kstart = knext;
           knext = A.key_off[key + 1];
+          moved = true;
         }
+        if (STREAM && moved) base = (uint32_t)(A.carry_prev[key] >> 32);
         seq = (uint32_t)(p - kstart);
       }
+      if (STREAM) seq += base;
       if (staged) {
         s_stage[so++] = uint2{key, seq};
       } else if (o < A.out_cap) {
@@ -736,6 +766,132 @@ __global__ void __launch_bounds__(kStThreads) stencil_emit(StencilArgs A) {
   }
 }
 
+// ---------------------------------------------------------------- streaming sessions
+// A key's stream goes on from batch to batch.  A run of a strict chain lives at most M events,
+// so all a key carries is one word: count << 32 | live, count its events so far and bit t of
+// live (t < H = M - 1) set when its last t + 1 events satisfy stages 0..t - a run waits in
+// stage t + 1.  One event with stage bits P (bit t = p_t(x)) steps it as
+// live' = ((live << 1) | 1) & P; bit M - 1 of live' is a match ending at the event and is
+// dropped (SURVEY A.5 over the concatenated stream).
+//
+// stencil_edge runs between stencil_mask and stencil_emit, a lane per key.  The head: the
+// carried live stepped over the key's first min(len, H) events of the batch.  A match there is
+// a window that begins in an earlier batch - wave_mask killed it as one crossing a key start,
+// so its bit is this kernel's alone to set, ORed into the word's 32-bit half (keys share words)
+// and counted for its stencil_emit block.  The tail: the state after the key's last event, from
+// live = 0 over its last H events (a run older than H events is gone), or the head's state when
+// the key has no more than H.  carry_next[k] = {count + len, live}; the session swaps the two
+// arrays after the batch, so stencil_emit (sequence numbers: count before the batch) and this
+// kernel read the same unmodified carry_prev.
+//
+// Two block-uniform routes, by the events the block's kEdgeKeys keys span.  Dense (the span
+// fits kEdgeTile events; a processor's micro-batches, many keys of a few events each): the
+// block streams the span once, 4 events a thread with 16-B loads, evaluates the stage bits of
+// every event into an LDS byte each, and the lanes walk their heads and tails out of LDS - no
+// event is loaded twice, no lane waits on a global load per event.  Sparse (long keys): a lane
+// reads its key's first and last H events itself, at most 2 H scalar loads per key against the
+// > kEdgeTile / kEdgeKeys events per key the mask pass streams.
+// kEdgeTile: a byte an event, 8 KiB a block; 8 blocks a CU (the 32 waves a CU holds) take
+// 64 KiB of its 160 KiB, so LDS never limits the occupancy.
+constexpr int kEdgeKeys = 256;
+constexpr int kEdgeTile = 8192;
+constexpr uint64_t kStGroupEvents = kStGroupChunks * kStWave;  // events per group count
+
+// c matches into counter g, for every lane of the wave: lanes with the same counter add once
+__device__ __forceinline__ void edge_count(uint32_t* group_cnt, uint32_t g, uint32_t c, int lane) {
+  uint64_t todo = __ballot(c != 0);
+  while (todo) {  // (wave-uniform)
+    const int j = __builtin_ctzll(todo);
+    const uint32_t gj = (uint32_t)__builtin_amdgcn_readlane((int)g, j);
+    const bool same = c != 0 && g == gj;
+    uint32_t sum = same ? c : 0u;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == j) atomicAdd(group_cnt + gj, sum);
+    todo &= ~__ballot(same);
+  }
+}
+
+template <class EV>
+__global__ void __launch_bounds__(kEdgeKeys) stencil_edge(StencilArgs A) {
+  constexpr int M = EV::STAGES, H = M - 1;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const uint64_t k0 = (uint64_t)blockIdx.x * kEdgeKeys, k = k0 + tid;
+  const bool valid = k < A.n_keys;
+  uint64_t s = 0, e = 0, word = 0;
+  if (valid) {
+    s = A.key_off[k];
+    e = A.key_off[k + 1];
+    word = A.carry_prev[k];
+  }
+  const uint64_t len = e - s;
+  if constexpr (H == 0) {  // a match is its own event: only the count advances
+    if (valid) A.carry_next[k] = word + (len << 32);
+  } else {
+    __shared__ uint32_t s_bits[kEdgeTile / 4 + 2];  // a byte per event from `base`
+    const EV ev(A);
+    const uint64_t k1 = k0 + kEdgeKeys < A.n_keys ? k0 + kEdgeKeys : A.n_keys;
+    const uint64_t b0 = A.key_off[k0], b1 = A.key_off[k1];  // the block's span
+    const bool dense = b1 - b0 <= (uint64_t)kEdgeTile;
+    const uint64_t base = b0 & ~3ull;  // (16-B loads: whole groups of 4 events)
+    if (dense) {
+      const uint32_t n4 = (uint32_t)((b1 - base + 3) / 4);  // <= kEdgeTile / 4 + 2
+      for (uint32_t g = tid; g < n4; g += kEdgeKeys) {
+        uint32_t P[M];
+#pragma unroll
+        for (int t = 0; t < M; t++) P[t] = 0;
+        ev.bits4(A, base + 4ull * g, P);  // (events past the batch's end stay 0)
+        uint32_t w = 0;
+#pragma unroll
+        for (int t = 0; t < M; t++)
+#pragma unroll
+          for (int i = 0; i < 4; i++) w |= ((P[t] >> i) & 1u) << (8 * i + t);
+        s_bits[g] = w;
+      }
+      __syncthreads();
+    }
+    // stage bits of event p (of this lane's key)
+    auto bits = [&](uint64_t p) -> uint32_t {
+      if (dense) return reinterpret_cast<const uint8_t*>(s_bits)[p - base];
+      uint32_t P[M];
+#pragma unroll
+      for (int t = 0; t < M; t++) P[t] = 0;
+      if constexpr (EV::RANGE) ev.range(ev.load1(A, p), P, 0);
+      else ev.one(A, p, P, 0);
+      uint32_t w = 0;
+#pragma unroll
+      for (int t = 0; t < M; t++) w |= (P[t] & 1u) << t;
+      return w;
+    };
+    constexpr uint32_t kLive = (1u << H) - 1u;
+    uint32_t live = (uint32_t)word & kLive;
+    // head: at most H events, in at most two groups
+    const uint32_t nh = len < (uint64_t)H ? (uint32_t)len : (uint32_t)H;
+    const uint32_t g0 = (uint32_t)(s / kStGroupEvents);
+    uint32_t c0 = 0, c1 = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < nh; i++) {
+      const uint64_t p = s + i;
+      live = ((live << 1) | 1u) & bits(p);
+      if (live >> H) {
+        atomicOr(reinterpret_cast<uint32_t*>(A.words + p / 64) + ((p >> 5) & 1), 1u << (p & 31));
+        if ((uint32_t)(p / kStGroupEvents) == g0) c0++;
+        else c1++;
+      }
+      live &= kLive;
+    }
+    edge_count(A.group_cnt, g0, c0, lane);
+    edge_count(A.group_cnt, g0 + 1, c1, lane);
+    if (len > (uint64_t)H) {  // tail
+      live = 0;
+#pragma unroll 1
+      for (uint64_t p = e - H; p < e; p++) live = ((live << 1) | 1u) & bits(p);
+      live &= kLive;
+    }
+    if (valid) A.carry_next[k] = (((word >> 32) + len) << 32) | live;
+  }
+}
+
 // ---------------------------------------------------------------- host launchers
 hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n_events, uint32_t* wave_key,
                             uint32_t* zero, uint32_t n_zero, hipStream_t st) {
@@ -748,15 +904,24 @@ hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n
 
 uint64_t stencil_waves(uint64_t n_events) { return (n_events + kStWave - 1) / kStWave; }
 
-// the mask kernel `mask` (an int32 or a typed instantiation for M stages), then the emit pass
-template <int M>
+// the mask kernel of evaluator EV (an int32 or a typed instantiation for M stages), then the emit
+// pass; a streaming session's batch (a.carry_prev): the edge kernel between them
+template <int M, class EV>
 static hipError_t launch_one(void (*mask)(StencilArgs), const StencilArgs& a, uint64_t n_tiles, hipStream_t st) {
   // (a separate build for the whole fast-path chunks, without the slow path's code and
   // registers, measured the same - 79.5 against 79.6 us for 1e8 events - and cost a launch)
   StencilArgs b = a;
   b.n_chunk = (a.n_events + kStWave - 1) / kStWave;
   hipLaunchKernelGGL(mask, dim3((uint32_t)((b.n_chunk + 3) / 4)), dim3(kStThreads), 0, st, b);
-  hipLaunchKernelGGL(stencil_emit<M>, dim3((uint32_t)((n_tiles + kEmW - 1) / kEmW)), dim3(kStThreads), 0, st, a);
+  const dim3 eg((uint32_t)((n_tiles + kEmW - 1) / kEmW));
+  if (a.carry_prev) {
+    if (a.n_keys)
+      hipLaunchKernelGGL(stencil_edge<EV>, dim3((uint32_t)((a.n_keys + kEdgeKeys - 1) / kEdgeKeys)), dim3(kEdgeKeys), 0,
+                         st, a);
+    hipLaunchKernelGGL((stencil_emit<M, true>), eg, dim3(kStThreads), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((stencil_emit<M, false>), eg, dim3(kStThreads), 0, st, a);
+  }
   return hipGetLastError();
 }
 
@@ -764,13 +929,13 @@ static hipError_t launch_one(void (*mask)(StencilArgs), const StencilArgs& a, ui
 // instantiations; any other, the typed ones
 template <int M>
 static hipError_t launch_m(const StencilArgs& a, bool range, int ncol, uint64_t n_tiles, hipStream_t st) {
-  if (!range) return launch_one<M>(stencil_mask<M, false, 1>, a, n_tiles, st);
+  if (!range) return launch_one<M, StEval<M, false, 1>>(stencil_mask<M, false, 1>, a, n_tiles, st);
   const int w0 = a.col_w[0], w1 = ncol > 1 ? a.col_w[1] : 0;
-  if (w0 == 4 && w1 == 0) return launch_one<M>(stencil_mask<M, true, 1>, a, n_tiles, st);
-  if (w0 == 4 && w1 == 4) return launch_one<M>(stencil_mask<M, true, 2>, a, n_tiles, st);
-  if (w0 == 8 && w1 == 0) return launch_one<M>(stencil_mask_typed<M, 8, 0>, a, n_tiles, st);
-  if (w0 == 4 && w1 == 8) return launch_one<M>(stencil_mask_typed<M, 4, 8>, a, n_tiles, st);
-  if (w0 == 8 && w1 == 8) return launch_one<M>(stencil_mask_typed<M, 8, 8>, a, n_tiles, st);
+  if (w0 == 4 && w1 == 0) return launch_one<M, StEval<M, true, 1>>(stencil_mask<M, true, 1>, a, n_tiles, st);
+  if (w0 == 4 && w1 == 4) return launch_one<M, StEval<M, true, 2>>(stencil_mask<M, true, 2>, a, n_tiles, st);
+  if (w0 == 8 && w1 == 0) return launch_one<M, StEvalT<M, 8, 0>>(stencil_mask_typed<M, 8, 0>, a, n_tiles, st);
+  if (w0 == 4 && w1 == 8) return launch_one<M, StEvalT<M, 4, 8>>(stencil_mask_typed<M, 4, 8>, a, n_tiles, st);
+  if (w0 == 8 && w1 == 8) return launch_one<M, StEvalT<M, 8, 8>>(stencil_mask_typed<M, 8, 8>, a, n_tiles, st);
   return hipErrorInvalidValue;  // (compile.cpp orders a mixed pair (4, 8))
 }
 

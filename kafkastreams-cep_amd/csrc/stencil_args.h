@@ -39,6 +39,10 @@ struct StencilArgs {
   // 64 w's sequence number within that key}
   uint4* words;
   uint32_t* group_cnt;       // matches per stencil_emit block's span (pass 1, atomics; zeroed per batch)
+  // streaming sessions (null otherwise): a word per key, count << 32 | live (stencil.hip
+  // stencil_edge).  A batch reads carry_prev and writes carry_next; the session swaps them
+  const uint64_t* carry_prev;
+  uint64_t* carry_next;
   // output
   uint32_t* m_key;
   uint32_t* p_seq;           // [n_matches * m]

@@ -23,7 +23,8 @@ partition (CEPProcessor.java:117-134), so records of different keys share runs; 
 processor keeps one NFA per key (a Kafka partition is usually one key's stream in the
 reference's demo, where both give the same matches).
 
-State.  The device session holds every key's NFA (run queue, shared buffer, folds).  The host
+State.  The device session holds every key's NFA (run queue, shared buffer, folds; for a
+strict chain, which runs on the stencil kernels, one carry word).  The host
 keeps, per key, only the records a later match can still contain: after each flush the
 session reports, per key, the oldest event a live buffer node holds (`cep_live_floor`) and
 older records are dropped - the same events the reference's buffer store still holds
