@@ -270,7 +270,8 @@ int cep_watermark(cep_session* s, int64_t* out);
  * loads a blob into a streaming session created over the same queries and max_runs; the
  * next cep_push_batch continues every key's stream where the snapshot left it.  Blobs from
  * other queries, options or versions are rejected with CEP_E_INVALID before any change.
- * A stencil-kind query's state is its carry array alone (8 bytes a key); a blob holding NFA
+ * A stencil-kind query's state is its carry array alone (8 bytes a key, and with semantic
+ * windows the key's last arity - 2 event times); a blob holding NFA
  * state for it (a force_nfa session's, or one written when streams ran such queries on the
  * NFA kernel) is rejected in the same way, and so is a carry array for a force_nfa session. */
 int cep_session_snapshot(cep_session* s, void* buf, size_t cap, size_t* size);
@@ -282,7 +283,10 @@ int cep_session_snapshot(cep_session* s, void* buf, size_t cap, size_t* size);
  * ones.  floor is host memory [n_keys]; n_keys <= the session's key space.
  * A stencil-kind query has no buffer: its floor comes from the carry word, the key's event
  * count less the length of its longest waiting run (live bit t: a run of the last t + 1
- * events), 0xFFFFFFFF when no run waits - exact, so never below the NFA path's floor. */
+ * events), 0xFFFFFFFF when no run waits - exact, so never below the NFA path's floor.
+ * With semantic windows the carry's live bits are not pruned by event time: a run the window
+ * has already dropped still counts, so the floor may be lower than a force_nfa session's - a
+ * host keeps a few more records, never too few. */
 int cep_live_floor(cep_session* s, int query, uint32_t* floor, uint64_t n_keys);
 int cep_session_restore(cep_session* s, const void* buf, size_t size);
 

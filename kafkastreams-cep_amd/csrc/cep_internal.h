@@ -35,6 +35,11 @@ struct cep_query {
   // window, so runs expire (the reference's own WITHIN never prunes: parity mode)
   bool semantic = false;
   bool windowed = false;            // semantic and some stage has a window
+  // CEP_KIND_STENCIL with semantic windows: position p (2 <= p < arity) of a match is held to
+  // stencilWin[p], the window of stage p - 1 (stencil.hip stencil_within); mask 0: no window can
+  // fire (stage 0's and the last stage's never do) and the query is an ordinary stencil query
+  int64_t stencilWin[cep::kMaxStencil];
+  uint32_t stencilWinMask = 0;
   int F = 2;                        // fold slots of a run record (states + the start slot)
   std::string jitSource;  // per-query NFA step policy for hipRTC (jit.cpp)
   std::shared_ptr<cep::ParsedQuery> parsed;  // the parsed chain and stage build (plan_groups)

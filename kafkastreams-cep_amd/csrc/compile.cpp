@@ -1308,8 +1308,9 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
   // CEP_KIND_STENCIL gate: every pattern ONE + STRICT, predicates total
   // and state-free (so evaluating them everywhere cannot throw or differ), distinct names.
   // The stencil kernels are instantiated for 1..kMaxStencil stages (stencil.hip
-  // launch_stencil); a longer strict chain runs on the NFA kernel.
-  bool stencil = np <= kMaxStencil && !q->windowed;  // (semantic windows: runs expire on ts)
+  // launch_stencil); a longer strict chain runs on the NFA kernel.  Semantic windows keep the
+  // stencil: an expired run of a strict chain is one more failed conjunct (stencilWin below).
+  bool stencil = np <= kMaxStencil;
   std::vector<int> seen;
   for (auto& p : ps) {
     if (p.card != CARD_ONE || p.strat != STRICT || !total(p.pred.get())) stencil = false;
@@ -1332,6 +1333,17 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
     }
     // stages were built last -> first; stage index of pattern i: $final=0, p_{m-1}=1, ..., p0=m
     for (int i = 0; i < np; i++) q->stencilProg[i] = d.st[np - i].e[0].prog;
+    // Semantic windows.  The run of a match that starts at event s sits, at event s + p
+    // (p >= 2), in the epsilon stage of stage p - 1 with start time ts[s + 1] (the epsilon stage
+    // after stage 0 is BEGIN-typed: no check at s + 1, the start restarts there), so it is
+    // dropped when window[stage p - 1] != -1 and ts[s + p] - ts[s + 1] exceeds it.  Stage 0's
+    // window and the last stage's never fire.
+    q->stencilWinMask = 0;
+    for (int p = 0; p < kMaxStencil; p++) q->stencilWin[p] = -1;
+    for (int p = 2; q->windowed && p < np; p++) {
+      q->stencilWin[p] = b.window[np - (p - 1)];
+      if (q->stencilWin[p] != -1) q->stencilWinMask |= 1u << p;
+    }
     // interval fast path: <= 8 stages, every predicate a conjunction of ranges over <= 2
     // shared columns (int, long or double each)
     std::vector<int> ftypes(d.field_type, d.field_type + nf);

@@ -197,6 +197,9 @@ struct QueryRt {
   // a streaming session's stencil query: a word per key (count << 32 | live, stencil.hip
   // stencil_edge).  A batch reads sc_carry[sc_cur] and writes the other; they swap after it
   DBuf sc_carry[2];
+  // and, with semantic windows (cep_query.stencilWinMask), the last arity - 2 event times of
+  // every key's stream (stencil.hip stencil_within), swapped with the carry words
+  DBuf sc_ts[2];
   int sc_cur = 0;
   uint64_t sc_keys = 0;
   bool sc_init = false;
@@ -336,6 +339,12 @@ void resolve(cep_session* s) {
   }
 }
 
+// bytes of a streaming session's carried event times (0: the query has no window that can fire)
+uint64_t stencil_ts_bytes(const cep_query* q, uint64_t n_keys) {
+  if (!q->stencilWinMask) return 0;
+  return sizeof(int64_t) * (q->info.arity - 2) * std::max<uint64_t>(n_keys, 1);
+}
+
 // a streaming session's carry arrays for n_keys keys (zero: every key in the initial state)
 void stencil_carry_init(cep_session* s, QueryRt& r, uint64_t n_keys) {
   const uint64_t bytes = sizeof(uint64_t) * std::max<uint64_t>(n_keys, 1);
@@ -343,11 +352,16 @@ void stencil_carry_init(cep_session* s, QueryRt& r, uint64_t n_keys) {
   r.sc_cur = 0;
   r.sc_keys = n_keys;
   HIPCHECK(hipMemsetAsync(r.sc_carry[0].p, 0, bytes, s->stream));
+  if (const uint64_t tb = stencil_ts_bytes(r.q, n_keys)) {
+    for (auto& c : r.sc_ts) c.ensure(tb);
+    HIPCHECK(hipMemsetAsync(r.sc_ts[0].p, 0, tb, s->stream));
+  }
   r.sc_init = true;
 }
 
 // Strict chains (stencil.hip): wave_keys, stencil_mask, stencil_emit; no host sync.  In a
-// streaming session stencil_edge runs between the two with the per-key carry.
+// streaming session stencil_edge runs between the two with the per-key carry; with semantic
+// windows stencil_within prunes the match words before stencil_emit.
 void run_stencil(cep_session* s, QueryRt& r) {
   const cep_query* q = r.q;
   const uint32_t m = q->info.arity;
@@ -421,7 +435,13 @@ void run_stencil(cep_session* s, QueryRt& r) {
       throw std::invalid_argument("the batches of a streaming session share one key space (n_keys)");
     a.carry_prev = r.sc_carry[r.sc_cur].as<uint64_t>();
     a.carry_next = r.sc_carry[r.sc_cur ^ 1].as<uint64_t>();
+    if (q->stencilWinMask) {
+      a.tsc_prev = r.sc_ts[r.sc_cur].as<int64_t>();
+      a.tsc_next = r.sc_ts[r.sc_cur ^ 1].as<int64_t>();
+    }
   }
+  a.win_mask = q->stencilWinMask;
+  for (int p = 0; p < kMaxStencil; p++) a.win[p] = q->stencilWin[p];
   // No event before wave_keys: every marker packet costs the stream ~5 us between kernels
   // (4 % of this 0.12 ms step), so the 4 us key-index pass is not timed (aux_ms 0).
   // wave_keys also zeroes the counters (no memset launch); no D2H copy of them either
@@ -431,7 +451,7 @@ void run_stencil(cep_session* s, QueryRt& r) {
   HIPCHECK(launch_stencil((int)m, a, range, q->nRangeCols, s->stream));
   HIPCHECK(hipEventRecord(r.tev[slot][2], s->stream));
   r.pending = true;
-  r.launches = streaming ? 3 : 2;  // stencil_mask (+ stencil_edge) + stencil_emit
+  r.launches = (streaming ? 3 : 2) + (q->stencilWinMask ? 1 : 0);  // stencil_mask (+ stencil_edge) (+ stencil_within) + stencil_emit
   if (streaming && s->n_events) r.sc_cur ^= 1;  // (an empty batch launches nothing: the carry stands)
   r.digest_valid = false;
   r.arity = m;
@@ -1513,7 +1533,8 @@ struct SnapQueryHdr {
   uint32_t F, rcap, node_used, pred_used, init, pad;
 };
 // SnapQueryHdr.init: 0 no state yet, 1 NFA state (StreamState), kSnapStencil a stencil query's
-// carry array alone (n_keys words).  A query restores only the kind of state its session runs.
+// carry array alone (n_keys words; with semantic windows the carried event times after them,
+// (arity - 2) x n_keys).  A query restores only the kind of state its session runs.
 constexpr uint32_t kSnapStencil = 2;
 
 uint64_t snap_size(const cep_session* s) {
@@ -1521,7 +1542,7 @@ uint64_t snap_size(const cep_session* s) {
   for (auto& r : s->qs) {
     n += sizeof(SnapQueryHdr);
     const StreamState& S = r->st;
-    if (r->sc_init) n += sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1);
+    if (r->sc_init) n += sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1) + stencil_ts_bytes(r->q, r->sc_keys);
     if (S.init)
       n += sizeof(KeyCarry) * std::max<uint64_t>(S.n_keys, 1) + S.ring_bytes + (sizeof(Node) + sizeof(Pred)) * S.node_used +
            sizeof(Pred) * S.pred_used;
@@ -1562,7 +1583,10 @@ int cep_session_snapshot(cep_session* s, void* buf, size_t cap, size_t* size) {
         if (n) copy_sync(o, src, n, hipMemcpyDeviceToHost, s->stream);
         o += n;
       };
-      if (r->sc_init) d2h(r->sc_carry[r->sc_cur].p, sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1));
+      if (r->sc_init) {
+        d2h(r->sc_carry[r->sc_cur].p, sizeof(uint64_t) * std::max<uint64_t>(r->sc_keys, 1));
+        d2h(r->sc_ts[r->sc_cur].p, stencil_ts_bytes(r->q, r->sc_keys));  // (its size: n_keys and the arity)
+      }
       if (!S.init) continue;
       d2h(S.carry.p, sizeof(KeyCarry) * std::max<uint64_t>(S.n_keys, 1));
       d2h(S.rings.p, S.ring_bytes);
@@ -1633,7 +1657,7 @@ int cep_session_restore(cep_session* s, const void* buf, size_t size) {
       if ((h.init == kSnapStencil) != (r->group < 0) || h.init > kSnapStencil)
         return fail(CEP_E_INVALID, "snapshot holds the query's state for the other path (stencil carry / NFA state)");
       if (h.init == kSnapStencil) {
-        const uint64_t n = sizeof(uint64_t) * std::max<uint64_t>(h.n_keys, 1);
+        const uint64_t n = sizeof(uint64_t) * std::max<uint64_t>(h.n_keys, 1) + stencil_ts_bytes(r->q, h.n_keys);
         if ((uint64_t)(end - q) < n) return fail(CEP_E_INVALID, "snapshot truncated");
         q += n;
         continue;
@@ -1664,6 +1688,10 @@ int cep_session_restore(cep_session* s, const void* buf, size_t size) {
         stencil_carry_init(s, *r, h.n_keys);
         copy_sync(r->sc_carry[0].p, q, n, hipMemcpyHostToDevice, s->stream);
         q += n;
+        if (const uint64_t tb = stencil_ts_bytes(r->q, h.n_keys)) {
+          copy_sync(r->sc_ts[0].p, q, tb, hipMemcpyHostToDevice, s->stream);
+          q += tb;
+        }
         continue;
       }
       auto h2d = [&](DBuf& dst, uint64_t n) {

@@ -24,7 +24,9 @@
 // for the two passes at round 5's start, profiles/r05/ - a tile waits for every tile before
 // it, ~24 look-back round trips deep within one round of co-resident tiles.)
 // In a streaming session stencil_edge runs between the two passes: a carry word per key settles
-// the windows that begin in an earlier batch (below, "streaming sessions").
+// the windows that begin in an earlier batch (below, "streaming sessions").  A query with
+// semantic windows runs stencil_within before stencil_emit: it clears the match bits whose
+// event times break a window (below, "semantic WITHIN").
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -892,6 +894,136 @@ __global__ void __launch_bounds__(kEdgeKeys) stencil_edge(StencilArgs A) {
   }
 }
 
+// ---------------------------------------------------------------- semantic WITHIN
+// With semantic windows (compile.cpp: an epsilon stage keeps its source stage's window) a run of
+// a strict chain is dropped at the event of position p (2 <= p < M) when stage p - 1 has a
+// window w and ts[s + p] - ts[s + 1] > w: the run's start time restarts at s + 1, because the
+// epsilon stage after stage 0 is BEGIN-typed, and the subtraction is Java's (wrapping, signed
+// compare).  Dropping it is the removePattern of a failed predicate on private nodes, so the
+// matches are the predicate windows whose time conditions all hold - a conjunct independent of
+// the stage bits.  stencil_within runs after stencil_mask (and stencil_edge) and before
+// stencil_emit: it clears the match bits that fail and takes them off the emit blocks' counts,
+// so stencil_emit reads what it would have read had the mask pass pruned.
+//
+// A wave owns the 64 word records of one mask chunk, a lane per word, and ballots the words
+// holding a match bit: the others cost their record load and nothing else, and event times
+// are read only around possible match ends.  Such a word is then the whole wave's: lane l
+// stands for the match ending at event 64 w + l, the word's 64 times (one coalesced 8-B load)
+// and the M - 2 before them (the halo) go to LDS once, and the start (lag M - 2) and the
+// constrained positions (lag M - 1 - p, a wave-uniform mask) are read from there.  The loads
+// of kWnBatch candidate words are in flight together.  A halo event before event 0, or before
+// the key's start, belongs to a window the mask pass has killed; it is not loaded.
+//
+// STREAM: a match ending in a key's first M - 1 events of the batch began in an earlier one.
+// Per key the session carries the last M - 2 event times of its stream (tsc_prev / tsc_next,
+// swapped as the carry words are); a lag that reaches before the key's first event of the
+// batch (the in-batch sequence number from the word record, or key_off where a key starts
+// inside the word) is taken from tsc_prev.  The blocks after the chunks' write tsc_next, a
+// lane per key: the last M - 2 times of tsc_prev followed by the key's events of the batch.
+// (The live bits of the carry word stay unpruned: a run the window has already dropped still
+// counts as live for cep_live_floor, which is then lower than it need be - never unsafe.)
+constexpr int kWnBatch = 4;
+
+// the time of event p (no times pushed: the event's position, as the NFA kernels take it)
+__device__ __forceinline__ int64_t event_time(const StencilArgs& A, uint64_t p) {
+  return A.ts ? A.ts[p] : (int64_t)p;
+}
+
+// LDS writes of a wave's lanes ordered before the reads of its other lanes (no instruction)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int M, bool STREAM>
+__global__ void __launch_bounds__(kStThreads) stencil_within(StencilArgs A) {
+  static_assert(M >= 3 && M <= kMaxStencil, "no position of a shorter chain is constrained");
+  constexpr int L = M - 2;  // the start's lag behind the match end
+  __shared__ int64_t s_t[kStThreads / 64][64 + L];  // a wave's word: events 64 w - L .. 64 w + 63
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t n_blocks = (uint32_t)((A.n_chunk + 3) / 4);  // the chunks' blocks
+  if (STREAM && blockIdx.x >= n_blocks) {  // (block-uniform) the keys' carried times
+    const uint64_t k = (uint64_t)(blockIdx.x - n_blocks) * kStThreads + threadIdx.x;
+    if (k >= A.n_keys) return;
+    const uint64_t s = A.key_off[k], e = A.key_off[k + 1], len = e - s;
+#pragma unroll
+    for (int x = 0; x < L; x++) {
+      const uint64_t r = (uint64_t)(L - 1 - x);  // events from the stream's end
+      A.tsc_next[k * L + x] = r < len ? event_time(A, e - 1 - r) : A.tsc_prev[k * L + (L - 1) - (r - len)];
+    }
+    return;
+  }
+  const uint64_t chunk = (uint64_t)blockIdx.x * (kStThreads / 64) + wv;
+  if (chunk >= A.n_chunk) return;  // (wave-uniform; no block-wide barrier below)
+  const uint64_t n_words = (A.n_events + 63) / 64;
+  const uint64_t w0 = chunk * (kStWave / 64);
+  const uint4 rec = w0 + lane < n_words ? A.words[w0 + lane] : uint4{0, 0, 0, 0};
+  uint64_t todo = __ballot((rec.x | rec.y) != 0);
+  int64_t* const st = s_t[wv];
+  uint32_t cleared = 0;  // (wave-uniform)
+  while (todo) {
+    int jw[kWnBatch];
+    int64_t tm[kWnBatch], th[kWnBatch];
+#pragma unroll
+    for (int b = 0; b < kWnBatch; b++) {
+      jw[b] = -1;
+      tm[b] = th[b] = 0;
+      if (todo) {
+        jw[b] = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint64_t e0 = (w0 + (uint64_t)jw[b]) * 64;  // (< n_events: the word exists)
+        if (e0 + lane < A.n_events) tm[b] = event_time(A, e0 + lane);
+        if (lane < L && e0 >= (uint64_t)L) th[b] = event_time(A, e0 - L + lane);
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < kWnBatch; b++) {
+      const int j = jw[b];
+      if (j < 0) break;
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, j);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, j);
+      const uint32_t wk = (uint32_t)__builtin_amdgcn_readlane((int)rec.z, j);
+      const uint32_t wsq = (uint32_t)__builtin_amdgcn_readlane((int)rec.w, j);
+      const uint64_t nat = ((uint64_t)hi << 32) | lo;
+      wave_sync();  // (the word before is read)
+      st[L + lane] = tm[b];
+      if (lane < L) st[lane] = th[b];
+      wave_sync();
+      const bool bit = (nat >> lane) & 1ull;
+      bool ok = true;
+      if (bit) {
+        // events of the lane's key in the batch before the match end: a lag beyond them is
+        // in an earlier batch (per-batch sessions: such a window is dead in the mask word)
+        uint64_t seq = ~0ull;
+        uint32_t key = wk & 0x7FFFFFFFu;
+        if (STREAM) {
+          seq = (uint64_t)wsq + (uint64_t)lane;
+          if (wk >> 31) {  // a key starts inside the word
+            const uint64_t p = (w0 + (uint64_t)j) * 64 + lane;
+            while (p >= A.key_off[key + 1]) key++;  // (p < n_events = key_off[n_keys])
+            seq = p - A.key_off[key];
+          }
+        }
+        auto lag = [&](int d) -> int64_t {
+          if (!STREAM || (uint64_t)d <= seq) return st[L + lane - d];
+          return A.tsc_prev[(uint64_t)key * L + (uint64_t)(L - d) + seq];  // (d - seq events before the batch)
+        };
+        const uint64_t t0 = (uint64_t)lag(L);
+#pragma unroll
+        for (int p = 2; p < M; p++)
+          if ((A.win_mask >> p) & 1u) ok = ok && (int64_t)((uint64_t)lag(M - 1 - p) - t0) <= A.win[p];
+      }
+      const uint64_t keep = nat & __ballot(ok);
+      if (keep != nat) {
+        cleared += (uint32_t)__popcll(nat ^ keep);
+        if (lane == j) *reinterpret_cast<uint2*>(A.words + w0 + j) = uint2{(uint32_t)keep, (uint32_t)(keep >> 32)};
+      }
+    }
+  }
+  if (lane == 0 && cleared) atomicSub(A.group_cnt + chunk / kStGroupChunks, cleared);
+}
+
 // ---------------------------------------------------------------- host launchers
 hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n_events, uint32_t* wave_key,
                             uint32_t* zero, uint32_t n_zero, hipStream_t st) {
@@ -905,7 +1037,8 @@ hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n
 uint64_t stencil_waves(uint64_t n_events) { return (n_events + kStWave - 1) / kStWave; }
 
 // the mask kernel of evaluator EV (an int32 or a typed instantiation for M stages), then the emit
-// pass; a streaming session's batch (a.carry_prev): the edge kernel between them
+// pass; a streaming session's batch (a.carry_prev): the edge kernel between them; semantic
+// windows (a.win_mask): stencil_within before the emit pass
 template <int M, class EV>
 static hipError_t launch_one(void (*mask)(StencilArgs), const StencilArgs& a, uint64_t n_tiles, hipStream_t st) {
   // (a separate build for the whole fast-path chunks, without the slow path's code and
@@ -914,12 +1047,19 @@ static hipError_t launch_one(void (*mask)(StencilArgs), const StencilArgs& a, ui
   b.n_chunk = (a.n_events + kStWave - 1) / kStWave;
   hipLaunchKernelGGL(mask, dim3((uint32_t)((b.n_chunk + 3) / 4)), dim3(kStThreads), 0, st, b);
   const dim3 eg((uint32_t)((n_tiles + kEmW - 1) / kEmW));
+  const uint32_t wg = (uint32_t)((b.n_chunk + 3) / 4);  // stencil_within: a wave per chunk's words
   if (a.carry_prev) {
     if (a.n_keys)
       hipLaunchKernelGGL(stencil_edge<EV>, dim3((uint32_t)((a.n_keys + kEdgeKeys - 1) / kEdgeKeys)), dim3(kEdgeKeys), 0,
                          st, a);
+    if constexpr (M >= 3)
+      if (a.win_mask)  // (and a lane per key after them: the carried times)
+        hipLaunchKernelGGL((stencil_within<M, true>), dim3(wg + (uint32_t)((a.n_keys + kStThreads - 1) / kStThreads)),
+                           dim3(kStThreads), 0, st, b);
     hipLaunchKernelGGL((stencil_emit<M, true>), eg, dim3(kStThreads), 0, st, a);
   } else {
+    if constexpr (M >= 3)
+      if (a.win_mask) hipLaunchKernelGGL((stencil_within<M, false>), dim3(wg), dim3(kStThreads), 0, st, b);
     hipLaunchKernelGGL((stencil_emit<M, false>), eg, dim3(kStThreads), 0, st, a);
   }
   return hipGetLastError();

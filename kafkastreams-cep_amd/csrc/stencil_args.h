@@ -43,6 +43,15 @@ struct StencilArgs {
   // stencil_edge).  A batch reads carry_prev and writes carry_next; the session swaps them
   const uint64_t* carry_prev;
   uint64_t* carry_next;
+  // semantic WITHIN (stencil.hip stencil_within; win_mask 0: the pass does not run).  A match of
+  // m events whose start is event s survives iff ts[s + p] - ts[s + 1] <= win[p] for every
+  // position p of win_mask (2 <= p < m; win[p]: the window of stage p - 1)
+  int64_t win[kMaxStencil];
+  uint32_t win_mask;
+  // streaming sessions: the last m - 2 event times of every key's stream, oldest first
+  // (tsc[k * (m - 2) + x]); read and written as the carry words are
+  const int64_t* tsc_prev;
+  int64_t* tsc_next;
   // output
   uint32_t* m_key;
   uint32_t* p_seq;           // [n_matches * m]
