@@ -97,9 +97,13 @@ typedef struct {
 
 #define CEP_KIND_NFA 0      /* general NFA kernel (runs, shared versioned buffer, folds) */
 #define CEP_KIND_STENCIL 1  /* proven specialisation: all stages ONE + strict, total
-                               state-free predicates, distinct names; range
-                               predicates over int, long and double columns take its fast
-                               path (cep_query_stencil_plan) */
+                               predicates, distinct names; a predicate is
+                               state-free or reads, with state.get, states that an earlier
+                               stage folds (a lagged chain: the read is that fold at a fixed
+                               lag inside the match); range predicates over int, long and
+                               double columns, and lagged compares of one such column, take
+                               its fast paths (cep_query_stencil_plan).  A streaming session
+                               runs a lagged chain on the NFA kernel */
 
 /* Compile a serialised Pattern chain.  On a reference compile-time exception the call
  * still succeeds and info.compile_error says which (sessions then refuse the query). */
@@ -128,9 +132,15 @@ int cep_query_group_plan(const cep_query* const* queries, int n_queries, int gro
  * stage a conjunction of `field OP constant`, OP in < <= > >= ==, over at most two columns of
  * int, long or double - the columns streamed with 16-B loads and compared as intervals, a mixed
  * pair listed int first) or interpreted predicates (anything else: a field under a cast, !=,
- * OR, NOT, arithmetic, ts, a third column).  (Introspection.) */
+ * OR, NOT, arithmetic, ts, a third column).  A lagged chain (a stage reads a state an earlier
+ * stage folds) has a fast path of its own: one column, every stage a conjunction of such range
+ * conjuncts and at most one `field OP state.get(X)` (either operand order, OP in < <= > >= ==)
+ * where X was last folded as the bare field - the column compared with itself a fixed 1..7
+ * events back, as values (a NaN fails, -0.0 == 0.0); any other lagged chain is interpreted.
+ * (Introspection.) */
 typedef struct {
-  uint32_t range;        /* 1: stencil_mask runs the range fast path; 0: interpreted predicates */
+  uint32_t range;        /* 1: stencil_mask runs the range fast path; 2: stencil_mask_lag, the lag fast
+                            path (n_cols 1); 0: interpreted predicates */
   uint32_t n_cols;       /* columns the fast path streams (1 or 2; 0 when range == 0) */
   uint32_t col_field[2]; /* their field indices */
   uint8_t  col_type[2];  /* the type each column is read as, IR type codes: 1 int, 2 long, 3 double.

@@ -31,6 +31,13 @@ struct cep_query {
   uint8_t rangeType[2] = {1, 1};      // IR types of rangeCols (a mixed pair: the int first)
   int nRangeCols = 0;
   int64_t rangeLo[8][2]{}, rangeHi[8][2]{};  // per stage and column, stencil_args.h RangeStage
+  // CEP_KIND_STENCIL, lagged chain (compile.cpp): stage t reads fold state x as the fold program
+  // lagProg[t][x] evaluated lagOf[t][x] events back (0: not read).  stencilLagFast: one column
+  // (rangeCols[0]), stage t holds rangeLo/Hi[t][0] and, where lagD[t] != 0, col[i] OP col[i - lagD[t]]
+  // (lagOp: 0 lt, 1 le, 2 gt, 3 ge, 4 eq) - stencil_lag.hip
+  bool stencilLag = false, stencilLagFast = false;
+  uint8_t lagOf[cep::kMaxStencil][cep::kMaxStates]{}, lagD[cep::kMaxStencil]{}, lagOp[cep::kMaxStencil]{};
+  uint16_t lagProg[cep::kMaxStencil][cep::kMaxStates]{};
   // semantic WITHIN (IR v2 flag): epsilon stages keep their source stage's
   // window, so runs expire (the reference's own WITHIN never prunes: parity mode)
   bool semantic = false;
@@ -116,6 +123,8 @@ hipError_t launch_wave_keys(const uint64_t* key_off, uint64_t n_keys, uint64_t n
                             uint32_t* zero, uint32_t n_zero, hipStream_t st);
 uint64_t stencil_waves(uint64_t n_events);
 hipError_t launch_stencil(int m, const StencilArgs& a, bool range, int ncol, hipStream_t st);
+// a lagged chain's mask kernel and the passes after it (stencil_lag.hip; per-batch sessions)
+hipError_t launch_stencil_lag(int m, const StencilArgs& a, bool fast, hipStream_t st);
 uint64_t stencil_tiles(uint64_t n_events);
 hipError_t launch_decode_stock_json(const uint8_t* bytes, const uint64_t* rec_off, uint64_t n, int col_width,
                                     void* price, void* volume, int32_t* status, uint32_t* name_span,

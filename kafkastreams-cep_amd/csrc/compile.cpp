@@ -166,13 +166,20 @@ struct PatternIR {
   std::vector<std::pair<uint16_t, std::unique_ptr<Expr>>> aggs;
 };
 
-bool total(const Expr* e) {  // evaluation can never throw
+// evaluation can never throw; `readable`: the fold states a state.get finds non-null (lagged chains)
+bool total(const Expr* e, uint32_t readable = 0) {
   if (!e) return true;
-  if (e->op == 0x07 || e->op == 0x09 || e->op == 0x08) return false;
+  if (e->op == 0x07) return e->idx < kMaxStates && ((readable >> e->idx) & 1u);
+  if (e->op == 0x09 || e->op == 0x08) return false;
   if ((e->op == 0x13 || e->op == 0x14) && e->t != 3) {
     if (!(e->b->op == 0x01 || e->b->op == 0x02) || e->b->i == 0) return false;
   }
-  return total(e->a.get()) && total(e->b.get());
+  return total(e->a.get(), readable) && total(e->b.get(), readable);
+}
+
+uint32_t state_reads(const Expr* e) {  // the states an expression reads with state.get
+  if (!e) return 0;
+  return (e->op == 0x07 && e->idx < kMaxStates ? 1u << e->idx : 0u) | state_reads(e->a.get()) | state_reads(e->b.get());
 }
 
 // The order key of a double (stencil_args.h RangeStage): int64 keys compare as the doubles do
@@ -276,6 +283,31 @@ bool ranges_of(const Expr* e, const std::vector<int>& ftypes, Ranges& r) {
     case 0x23: return r.add(f->idx, ft, k, INT64_MAX);
     default: return r.add(f->idx, ft, k, k);
   }
+}
+
+// IR type of a total fold expression (a field's own comes from the schema)
+int expr_type(const Expr* e, const std::vector<int>& ftypes) { return e->op == 0x05 ? ftypes[e->idx] : e->t; }
+
+// A stage of the lag fast route (stencil_lag.hip StEvalLag): a conjunction of range conjuncts
+// (ranges_of) and at most one lag conjunct `field OP state.get(X)`, either operand order, OP in
+// < <= > >= ==, compared in the field's own type.  *n counts the lag conjuncts; *op is the
+// operator with the field on the left (0 lt, 1 le, 2 gt, 3 ge, 4 eq).
+bool lag_conjuncts(const Expr* e, const std::vector<int>& ftypes, Ranges& r, int* field, int* op, int* state, int* n) {
+  if (e->op == 0x30)
+    return lag_conjuncts(e->a.get(), ftypes, r, field, op, state, n) &&
+           lag_conjuncts(e->b.get(), ftypes, r, field, op, state, n);
+  if (e->op >= 0x20 && e->op <= 0x24 && (e->a->op == 0x07 || e->b->op == 0x07)) {
+    const bool left = e->a->op == 0x07;  // state.get(X) OP field  ->  field OP' state.get(X)
+    const Expr* f = left ? e->b.get() : e->a.get();
+    const Expr* x = left ? e->a.get() : e->b.get();
+    if (f->op != 0x05 || e->t2 < 1 || e->t2 > 3 || ftypes[f->idx] != e->t2 || (*n)++) return false;
+    static const int flip[5] = {2, 3, 0, 1, 4};
+    *field = f->idx;
+    *op = left ? flip[e->op - 0x20] : e->op - 0x20;
+    *state = x->idx;
+    return true;
+  }
+  return ranges_of(e, ftypes, r);
 }
 
 enum { CARD_ONE = 0, CARD_OPTIONAL = 1, CARD_ZOM = 2, CARD_OOM = 3 };
@@ -1310,10 +1342,37 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
   // The stencil kernels are instantiated for 1..kMaxStencil stages (stencil.hip
   // launch_stencil); a longer strict chain runs on the NFA kernel.  Semantic windows keep the
   // stencil: an expired run of a strict chain is one more failed conjunct (stencilWin below).
+  //
+  // Lagged chains.  A stage t may read a state X with state.get when some stage u < t folds it:
+  // a run of such a chain never branches and keeps the sequence id it was created with
+  // (NFA.java:148-157; the begin run is re-created with a new id after every event), folds are
+  // stored under (state, id) after the stage's predicate matched (:259-265), so what stage t
+  // reads at event s + t is the fold of the largest u < t folding X, evaluated at event s + u -
+  // never null, never another run's.  With that fold total, state-free and of X's type, the
+  // read is the fold expression at the event t - u back and the predicate with it substituted
+  // must be total.  Anything else (getOrElse, curr, a state no earlier stage folds - null in
+  // the reference - or folds twice in that stage) keeps the NFA kernel.
   bool stencil = np <= kMaxStencil;
+  struct LagSrc { int stage = -1, agg = 0; };  // the stage and fold that supply a state read
+  std::vector<std::vector<LagSrc>> lagSrc(np, std::vector<LagSrc>(kMaxStates));
+  std::vector<int> ftypes(d.field_type, d.field_type + nf);
   std::vector<int> seen;
-  for (auto& p : ps) {
-    if (p.card != CARD_ONE || p.strat != STRICT || !total(p.pred.get())) stencil = false;
+  for (int t = 0; t < np; t++) {
+    auto& p = ps[t];
+    uint32_t readable = 0;
+    for (int x = 0; x < ns; x++)
+      for (int u = t - 1; u >= 0; u--) {
+        int cnt = 0, k = 0;
+        for (size_t a = 0; a < ps[u].aggs.size(); a++)
+          if (ps[u].aggs[a].first == x) { cnt++; k = (int)a; }
+        if (cnt == 0) continue;
+        if (cnt == 1 && expr_type(ps[u].aggs[k].second.get(), ftypes) == d.state_type[x]) {
+          readable |= 1u << x;
+          lagSrc[t][x] = LagSrc{u, k};
+        }
+        break;
+      }
+    if (p.card != CARD_ONE || p.strat != STRICT || !total(p.pred.get(), readable)) stencil = false;
     // folds never influence a stencil match, but they run on every BEGIN and can throw
     // (a null `curr` unboxed, integer division): only total folds keep the stencil exact
     for (auto& a : p.aggs)
@@ -1346,7 +1405,6 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
     }
     // interval fast path: <= 8 stages, every predicate a conjunction of ranges over <= 2
     // shared columns (int, long or double each)
-    std::vector<int> ftypes(d.field_type, d.field_type + nf);
     bool range = np <= 8;
     int cols[2] = {-1, -1}, ctype[2] = {1, 1}, ncols = 0;
     for (int i = 0; i < np && range; i++) {
@@ -1383,6 +1441,51 @@ void compile_query(const uint8_t* ir, size_t n, cep_query* q) {
     // (no column constrained: column 0 read as ints, every value accepted)
     q->rangeType[0] = (uint8_t)ctype[0];
     q->rangeType[1] = ncols < 2 ? q->rangeType[0] : (uint8_t)ctype[1];
+    // Lagged chains: per stage the states it reads, the fold program that supplies each and the
+    // lag (a state read is no range: stencilRange is false here)
+    q->stencilLag = q->stencilLagFast = false;
+    std::memset(q->lagOf, 0, sizeof q->lagOf);
+    std::memset(q->lagProg, 0, sizeof q->lagProg);
+    for (int t = 0; t < np; t++) {
+      const uint32_t reads = state_reads(ps[t].pred.get());
+      for (int x = 0; x < ns; x++) {
+        if (!((reads >> x) & 1u)) continue;
+        const LagSrc& src = lagSrc[t][x];
+        q->stencilLag = true;
+        q->lagOf[t][x] = (uint8_t)(t - src.stage);
+        q->lagProg[t][x] = d.st[np - src.stage].agg_prog[src.agg];
+      }
+    }
+    // the lag fast route: one column of int, long or double, every stage ranges on it and at
+    // most one lag conjunct whose state resolves to the bare column
+    bool fast = q->stencilLag;
+    int col = -1;
+    for (int t = 0; t < np && fast; t++) {
+      Ranges r;
+      int f = -1, op = 0, x = -1, n = 0;
+      if (!lag_conjuncts(ps[t].pred.get(), ftypes, r, &f, &op, &x, &n) || r.n > 1 || (n && r.n && r.field[0] != f)) {
+        fast = false;
+        break;
+      }
+      const int c = n ? f : r.n ? r.field[0] : col;
+      if (col >= 0 && c != col) fast = false;
+      col = c;
+      q->lagD[t] = q->lagOp[t] = 0;
+      if (n) {
+        const Expr* fold = ps[lagSrc[t][x].stage].aggs[lagSrc[t][x].agg].second.get();
+        if (fold->op != 0x05 || fold->idx != f) fast = false;
+        q->lagD[t] = q->lagOf[t][x];
+        q->lagOp[t] = (uint8_t)op;
+      }
+      q->rangeLo[t][0] = r.n ? r.lo[0] : INT64_MIN;
+      q->rangeHi[t][0] = r.n ? r.hi[0] : INT64_MAX;
+    }
+    if (fast) {
+      q->stencilLagFast = true;
+      q->nRangeCols = 1;
+      q->rangeCols[0] = q->rangeCols[1] = col;
+      q->rangeType[0] = q->rangeType[1] = (uint8_t)ftypes[col];
+    }
   } else {
     q->info.kind = CEP_KIND_NFA;
     q->info.arity = 0;

@@ -419,6 +419,12 @@ void run_stencil(cep_session* s, QueryRt& r) {
     }
   }
   for (uint32_t x = 0; x < m && x < (uint32_t)kMaxStencil; x++) a.stage_name[x] = q->arityStage[x];
+  if (q->stencilLag) {  // a lagged chain: the states its stages read, as fold programs at lags
+    std::memcpy(a.lag_of, q->lagOf, sizeof a.lag_of);
+    std::memcpy(a.lag_prog, q->lagProg, sizeof a.lag_prog);
+    std::memcpy(a.lag_d, q->lagD, sizeof a.lag_d);
+    std::memcpy(a.lag_op, q->lagOp, sizeof a.lag_op);
+  }
   a.words = s->mask.as<uint4>();
   a.group_cnt = reinterpret_cast<uint32_t*>(sc + 1);
   a.m_key = r.m_key.as<uint32_t>();
@@ -448,7 +454,8 @@ void run_stencil(cep_session* s, QueryRt& r) {
   HIPCHECK(launch_wave_keys(s->key_off, nk, s->n_events, s->keylist.as<uint32_t>(), reinterpret_cast<uint32_t*>(sc),
                             (uint32_t)((sizeof(Scratch) + sizeof(uint32_t) * n_groups) / 4), s->stream));
   HIPCHECK(hipEventRecord(r.tev[slot][1], s->stream));
-  HIPCHECK(launch_stencil((int)m, a, range, q->nRangeCols, s->stream));
+  if (q->stencilLag) HIPCHECK(launch_stencil_lag((int)m, a, q->stencilLagFast, s->stream));
+  else HIPCHECK(launch_stencil((int)m, a, range, q->nRangeCols, s->stream));
   HIPCHECK(hipEventRecord(r.tev[slot][2], s->stream));
   r.pending = true;
   r.launches = (streaming ? 3 : 2) + (q->stencilWinMask ? 1 : 0);  // stencil_mask (+ stencil_edge) (+ stencil_within) + stencil_emit
@@ -1055,8 +1062,8 @@ int cep_query_stencil_plan(const cep_query* q, cep_stencil_plan* out) {
   if (!q || !out) return fail(CEP_E_INVALID, "bad argument");
   if (q->info.kind != CEP_KIND_STENCIL) return fail(CEP_E_INVALID, "not a stencil query");
   *out = cep_stencil_plan{};
-  if (!q->stencilRange) return CEP_OK;
-  out->range = 1;
+  if (!q->stencilRange && !q->stencilLagFast) return CEP_OK;
+  out->range = q->stencilLagFast ? 2 : 1;
   out->n_cols = (uint32_t)q->nRangeCols;
   for (int c = 0; c < q->nRangeCols; c++) {
     out->col_field[c] = (uint32_t)q->rangeCols[c];
@@ -1108,7 +1115,9 @@ int cep_session_create(const cep_query* const* queries, int n_queries, const cep
     // literals as one launch (plan_groups); streams and the interpreter run one query each
     std::vector<int> nfa;
     for (int i = 0; i < n_queries; i++)
-      if (queries[i]->info.kind == CEP_KIND_NFA || s->opts.force_nfa) nfa.push_back(i);
+      // (a lagged chain in a streaming session: the carry word does not hold the lagged values)
+      if (queries[i]->info.kind == CEP_KIND_NFA || s->opts.force_nfa || (queries[i]->stencilLag && s->opts.streaming))
+        nfa.push_back(i);
     std::vector<GroupPlan> plans;
     if (s->opts.tier == CEP_TIER_JIT && !s->opts.streaming && !s->opts.no_groups) {
       std::vector<const cep_query*> qv;

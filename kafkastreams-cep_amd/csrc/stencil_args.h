@@ -59,6 +59,13 @@ struct StencilArgs {
   uint64_t* total_host;      // the same, into the session's pinned host copy (no D2H copy per batch)
   uint64_t out_cap;          // matches that fit the output arrays
   uint32_t* overflow;
+  // lagged strict chains (stencil_lag.hip; compile.cpp): stage s reads fold state X as the fold
+  // program lag_prog[s][X] evaluated lag_of[s][X] events back (0: the stage does not read X)
+  uint16_t lag_prog[kMaxStencil][kMaxStates];
+  uint8_t lag_of[kMaxStencil][kMaxStates];
+  // the lag fast route: stage s holds rs[s] on col[0] and col[0][i] OP col[0][i - lag_d[s]]
+  // (lag_d 0: no such conjunct; lag_op: 0 lt, 1 le, 2 gt, 3 ge, 4 eq, compared as values)
+  uint8_t lag_d[kMaxStencil], lag_op[kMaxStencil];
 };
 
 }  // namespace cep

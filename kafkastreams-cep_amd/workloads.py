@@ -61,6 +61,16 @@ def strict_abc_query(schema: EventSchema | None = None):
             .select("C").where(lambda k, v, ts, s: v.v >= 8).build())
 
 
+def rising_query(m: int = 3, type: str = "int"):
+    """SEQ of m strict stages, each value above the one before ("m rising ticks"): a stage folds
+    its value into "p" and the next reads it - a lagged strict chain (lag 1 everywhere)."""
+    b = QueryBuilder(EventSchema({"v": type}))
+    for i in range(m):
+        sel = b.select(f"S{i}").where((lambda k, v, ts, s: v.v > s.get("p")) if i else (lambda k, v, ts, s: v.v >= 0))
+        b = sel.fold("p", lambda k, v, c: v.v).then() if i < m - 1 else sel
+    return b.build()
+
+
 def any_kleene_query(schema: EventSchema | None = None, carry_volume: bool = False):
     """Config 4: skip_till_any Kleene+ with folds and a tight WITHIN (run-explosion stress).
 
